@@ -16,6 +16,15 @@ is active during the whole timed region — nothing is skipped.
 
 Usage: python bench.py --gpus N --steps K --warmup W
 (for N>1 the driver launches via torch.distributed.run, one rank per GPU).
+
+A plain run sets up, warms up, times the K steps and prints one JSON result
+line. ``--dump-outputs DIR`` additionally writes what the last timed step
+computed (action, reward, next observation, solver solution and the
+networks' parameters after ``learn()``) as ``DIR/<name>.npy`` in float32;
+with the same arguments the inputs are the same from run to run, so two
+builds can be compared output for output. ``--full`` is where any further
+measurement beyond the headline figure belongs; none exists today, so it
+runs the same path.
 """
 
 from __future__ import annotations
@@ -37,6 +46,27 @@ N = 20
 M = 20
 
 
+def dump_outputs(out_dir, obs, last, env, agent):
+    """Write what the last timed step handed back to its caller — action,
+    reward, next observation, the env's solver solution — and every
+    network's flat parameters after that step's learn(), one float32
+    ``<name>.npy`` each (about 7 MB in all at this config)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {
+        "action": last["action"],
+        "reward": last["reward"],
+        "obs_A": obs["A"],
+        "obs_eig": obs["eig"],
+        "solution_x": env.x,
+    }
+    for name, fp in sorted(vars(agent).items()):
+        if name.endswith("_fp"):
+            arrays[name[:-3] + "_params"] = fp.flat
+    for name, v in arrays.items():
+        v = torch.as_tensor(v).detach().to("cpu", torch.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), v.numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -50,7 +80,14 @@ def main():
     # BASELINE config 2: elastic-net TD3 + prioritized replay, bf16
     ap.add_argument("--algo", choices=["sac", "td3"], default="sac")
     ap.add_argument("--dtype", choices=["fp32", "bf16"], default="fp32")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/*.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beyond the headline "
+                         "figure (none today)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.dtype == "bf16":
         from smartcal_amd.ops import linear as linear_ops
@@ -98,6 +135,7 @@ def main():
 
     obs = env.reset()
     zeros2 = np.zeros(2, dtype=np.float32)
+    last = {}   # action and reward of the latest step (for --dump-outputs)
 
     if have_gpu:
         # sync-free training step: action, reward and observation stay on
@@ -107,6 +145,7 @@ def main():
             o2, r, done, info = env.step(a)
             agent.store_transition(o, a, r, o2, done, zeros2)
             agent.learn()
+            last["action"], last["reward"] = a, r
             return o2
     else:
         def one_step(o):
@@ -114,6 +153,7 @@ def main():
             o2, r, done, info = env.step(a)
             agent.store_transition(o, a, r, o2, done, zeros2)
             agent.learn()
+            last["action"], last["reward"] = a, r
             return o2
 
     # ---- pre-fill replay so learn() is live in the timed region ----
@@ -180,6 +220,9 @@ def main():
     total_steps = args.steps * max(world, 1)
     value = total_steps / elapsed_max
     ms_per_step = elapsed_max / args.steps * 1000.0
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, obs, last, env, agent)
 
     if rank == 0:
         algo = args.algo.upper()

@@ -50,7 +50,12 @@ def main():
     acc = float((pred == y).float().mean())
     print(f"accuracy over {n} samples: {acc:.3f}")
 
-    # harvest LBFGS curvature pairs then influence matrix
+    # harvest LBFGS curvature pairs then influence matrix. The influence
+    # matrix differentiates the input gradient a second time, which the
+    # HIP fused kernels do not support (ops/linear.py, CONTRACT
+    # RESTRICTION), so this check runs on the CPU path, which has no such
+    # restriction.
+    net, x, y = net.cpu(), x.cpu(), y.cpu()
     opt = LBFGSNew(net.parameters(), history_size=7, max_iter=4,
                    line_search_fn=True, batch_mode=True)
     for _ in range(4):

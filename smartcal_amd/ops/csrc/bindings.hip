@@ -324,24 +324,35 @@ std::tuple<at::Tensor, at::Tensor> als_sweep(
 }
 
 // Direct-accumulate variant of fused_linear_bwd_dz: dgamma/dbeta are
-// (pre-zeroed) flat-grad views accumulated atomically by the kernel.
+// (pre-zeroed) flat-grad views the kernel adds its column sums into
+// (fixed summation order, no atomics). Pass None for both when the sums
+// are not wanted (frozen parameters): the kernel then skips them.
 at::Tensor fused_linear_bwd_dz_into(
     const at::Tensor& dy, const at::Tensor& y, const at::Tensor& zhat,
     const at::Tensor& rstd, const c10::optional<at::Tensor>& gamma,
-    int64_t act, bool with_ln, at::Tensor dgamma, at::Tensor dbeta) {
+    int64_t act, bool with_ln, const c10::optional<at::Tensor>& dgamma,
+    const c10::optional<at::Tensor>& dbeta) {
   check_f32(dy, "dy");
   const int B = dy.size(0), N = dy.size(1);
   auto dz = at::empty({B, N}, dy.options());
-  TORCH_CHECK(dgamma.is_contiguous() && dbeta.is_contiguous(),
-              "grad views must be contiguous");
+  const bool want_cols = dgamma.has_value();
+  TORCH_CHECK(dbeta.has_value() == want_cols,
+              "dgamma and dbeta are given together or not at all");
+  if (want_cols) {
+    check_f32(*dgamma, "dgamma");
+    check_f32(*dbeta, "dbeta");
+    TORCH_CHECK(dgamma->numel() == N && dbeta->numel() == N,
+                "grad views must have N elements");
+  }
   hipLaunchKernelGGL(ln_act_bwd_kernel, dim3(B), dim3(256), 0, stream(),
                      dy.data_ptr<float>(), y.data_ptr<float>(),
                      with_ln ? zhat.data_ptr<float>() : nullptr,
                      with_ln ? rstd.data_ptr<float>() : nullptr,
                      gamma ? gamma->data_ptr<float>() : nullptr,
-                     dz.data_ptr<float>(), dgamma.data_ptr<float>(),
-                     dbeta.data_ptr<float>(), B, N, (int)act,
-                     with_ln ? 1 : 0);
+                     dz.data_ptr<float>(),
+                     want_cols ? dgamma->data_ptr<float>() : nullptr,
+                     want_cols ? dbeta->data_ptr<float>() : nullptr, B, N,
+                     (int)act, with_ln ? 1 : 0);
   return dz;
 }
 

@@ -247,8 +247,8 @@ extern "C" __global__ __launch_bounds__(256) void ln_act_bwd_kernel(
     const float* __restrict__ RSTD, // (B,)
     const float* __restrict__ gamma,// (N)
     float* __restrict__ DZ,         // (B, N)
-    float* __restrict__ DGAMMA,     // (N) pre-zeroed, atomically accumulated
-    float* __restrict__ DBETA,      // (N)
+    float* __restrict__ DGAMMA,     // (N) accumulated into (+=); may be null
+    float* __restrict__ DBETA,      // (N) with DGAMMA
     int B, int N, int act, int with_ln) {
   __shared__ float red[2 * 4];  // per-wave partial sums (m1, m2)
   const int row = blockIdx.x;
@@ -263,6 +263,43 @@ extern "C" __global__ __launch_bounds__(256) void ln_act_bwd_kernel(
     return;
   }
 
+  // dgamma/dbeta column sums without float atomics, so that they are
+  // bitwise reproducible: workgroup `row` also owns the column slice
+  // [row*cpb, (row+1)*cpb) and sums it over all B rows in a fixed order
+  // (one wave per column, lanes stride the rows, butterfly wave_sum).
+  // The terms depend only on the kernel's inputs, so no grid sync is
+  // needed. DGAMMA == nullptr: the caller does not want these sums.
+  const int nw = (blockDim.x + 63) / 64;
+  const int lane = tid & 63;
+  const bool want_cols = DGAMMA != nullptr;
+  const int cpb = (N + (int)gridDim.x - 1) / (int)gridDim.x;
+  const int c0 = row * cpb;
+  const int c1 = min(N, c0 + cpb);
+  // Common shape (B <= 64, at most two columns per wave): issue the
+  // column loads now and reduce them after the row work, so that their
+  // latency hides behind it instead of adding a round trip at the end.
+  const bool cols_early = want_cols && B <= 64 && cpb <= 2 * nw;
+  float cdy[2] = {0.f, 0.f}, cy[2] = {0.f, 0.f}, czh[2] = {0.f, 0.f};
+  float gold[2] = {0.f, 0.f}, bold[2] = {0.f, 0.f};
+  if (cols_early) {
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int c = c0 + wave + k * nw;
+      if (c < c1) {
+        if (lane < B) {
+          const long i = (long)lane * N + c;
+          cdy[k] = DY[i];
+          cy[k] = Yv[i];
+          czh[k] = ZHAT[i];
+        }
+        if (lane == 0) {
+          gold[k] = DGAMMA[c];
+          bold[k] = DBETA[c];
+        }
+      }
+    }
+  }
+
   float m1 = 0.f, m2 = 0.f;
   for (int c = tid; c < N; c += blockDim.x) {
     const long i = (long)row * N + c;
@@ -271,18 +308,15 @@ extern "C" __global__ __launch_bounds__(256) void ln_act_bwd_kernel(
     const float dzh = dh * gamma[c];
     m1 += dzh;
     m2 += dzh * zh;
-    atomicAdd(&DGAMMA[c], dh * zh);
-    atomicAdd(&DBETA[c], dh);
   }
   m1 = wave_sum(m1);
   m2 = wave_sum(m2);
-  if ((tid & 63) == 0) {
+  if (lane == 0) {
     red[wave * 2 + 0] = m1;
     red[wave * 2 + 1] = m2;
   }
   __syncthreads();
   float M1 = 0.f, M2 = 0.f;
-  const int nw = (blockDim.x + 63) / 64;
   for (int w = 0; w < nw; ++w) {
     M1 += red[w * 2 + 0];
     M2 += red[w * 2 + 1];
@@ -295,6 +329,39 @@ extern "C" __global__ __launch_bounds__(256) void ln_act_bwd_kernel(
     const float dh = DY[i] * act_grad_from_y(Yv[i], act);
     const float dzh = dh * gamma[c];
     DZ[i] = rstd * (dzh - M1 - ZHAT[i] * M2);
+  }
+
+  if (cols_early) {
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int c = c0 + wave + k * nw;
+      if (c < c1) {  // wave-uniform
+        // lanes >= B hold zeros: dh = 0 for them
+        const float dh = cdy[k] * act_grad_from_y(cy[k], act);
+        const float sg = wave_sum(dh * czh[k]);
+        const float sb = wave_sum(dh);
+        if (lane == 0) {
+          DGAMMA[c] = gold[k] + sg;
+          DBETA[c] = bold[k] + sb;
+        }
+      }
+    }
+  } else if (want_cols) {
+    for (int c = c0 + wave; c < c1; c += nw) {
+      float sg = 0.f, sb = 0.f;
+      for (int b = lane; b < B; b += 64) {
+        const long i = (long)b * N + c;
+        const float dh = DY[i] * act_grad_from_y(Yv[i], act);
+        sg += dh * ZHAT[i];
+        sb += dh;
+      }
+      sg = wave_sum(sg);
+      sb = wave_sum(sb);
+      if (lane == 0) {
+        DGAMMA[c] += sg;
+        DBETA[c] += sb;
+      }
+    }
   }
 }
 

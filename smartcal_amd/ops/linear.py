@@ -61,21 +61,6 @@ def get_compute_dtype() -> str:
     return _COMPUTE_DTYPE
 
 
-_scratch: dict = {}
-
-
-def _scratch_buf(n: int, device) -> torch.Tensor:
-    """Reusable throwaway accumulation buffer for dgamma/dbeta when the
-    parameter grads are not wanted (frozen-critic actor phase): avoids
-    two at::zeros fill kernels per layer per backward."""
-    key = (device.type, device.index)
-    buf = _scratch.get(key)
-    if buf is None or buf.numel() < n:
-        buf = torch.empty(max(n, 1024), device=device)
-        _scratch[key] = buf
-    return buf[:n]
-
-
 def _grad_view(p: torch.Tensor) -> torch.Tensor:
     """The tensor the kernels accumulate this parameter's gradient into.
 
@@ -117,13 +102,9 @@ class _FusedLinearFn(torch.autograd.Function):
                 dy, y, zhat, rstd, gamma, ctx.act_code, True,
                 _grad_view(gp), _grad_view(bep))
         elif ctx.with_ln:
-            # grads not wanted (frozen params): accumulate into a
-            # reusable scratch buffer instead of fresh zeros
-            n = dy.shape[1]
-            sb = _scratch_buf(2 * n, dy.device)
+            # grads not wanted (frozen params): no dgamma/dbeta sums
             dz = ext().fused_linear_bwd_dz_into(
-                dy, y, zhat, rstd, gamma, ctx.act_code, True,
-                sb[:n], sb[n:2 * n])
+                dy, y, zhat, rstd, gamma, ctx.act_code, True, None, None)
         else:
             dz, _, _ = ext().fused_linear_bwd_dz(
                 dy, y, zhat, rstd, gamma, ctx.act_code, False)
@@ -248,11 +229,9 @@ class _FusedChainFn(torch.autograd.Function):
                     dy, ys[l], zhats[l], rstds[l], g, ctx.acts[l], True,
                     _grad_view(g), _grad_view(be))
             else:
-                n = dy.shape[1]
-                sb = _scratch_buf(2 * n, dy.device)
                 dz = ext().fused_linear_bwd_dz_into(
                     dy, ys[l], zhats[l], rstds[l], g, ctx.acts[l], True,
-                    sb[:n], sb[n:2 * n])
+                    None, None)
             x_l = x if l == 0 else ys[l - 1]
             if getattr(ctx, "bf16", False):
                 if want_w:

@@ -227,7 +227,10 @@ def test_bench_torchrun_world2_cpu(tmp_path):
     import subprocess, os, sys
     from pathlib import Path
     ROOT = Path(__file__).resolve().parents[1]
-    env = dict(os.environ, PYTHONPATH=str(ROOT))
+    # CPU/gloo launch: hide any GPU, or each rank would claim the
+    # device numbered by its local rank
+    env = dict(os.environ, PYTHONPATH=str(ROOT),
+               CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="")
     r = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
          "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
@@ -369,7 +372,10 @@ def test_bench_torchrun_world8_cpu(tmp_path):
     import subprocess, os, sys
     from pathlib import Path
     ROOT = Path(__file__).resolve().parents[1]
-    env = dict(os.environ, PYTHONPATH=str(ROOT))
+    # CPU/gloo launch: hide any GPU, or each rank would claim the
+    # device numbered by its local rank
+    env = dict(os.environ, PYTHONPATH=str(ROOT),
+               CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="")
     r = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
          "--nproc-per-node", "8", "--master-addr", "127.0.0.1",

@@ -44,8 +44,14 @@ def test_fused_linear_fwd_matches_cpu():
         assert torch.allclose(y2.cpu(), ref2, atol=2e-4)
 
 
+# dgamma/dbeta column sums take two paths in the backward kernel: loads
+# issued early when B <= 64 and each workgroup owns <= 8 columns
+# ((64, 420, 512); (40, 9, 200) leaves some waves one or no column), else
+# a loop ((4, 7, 64), (5, 2, 192); (100, 9, 64) has more rows than a wave
+# and more workgroups than columns).
 @pytest.mark.parametrize("B,K,N", [(64, 420, 512), (4, 7, 64),
-                                   (5, 2, 192)])
+                                   (5, 2, 192), (40, 9, 200),
+                                   (100, 9, 64)])
 def test_fused_linear_backward_matches_cpu(B, K, N):
     torch.manual_seed(0)
     x = torch.randn(B, K)
@@ -84,6 +90,74 @@ def test_fused_linear_backward_matches_cpu(B, K, N):
         err = (gpu_t.cpu() - cpu_t).abs().max()
         denom = cpu_t.abs().max().clamp_min(1.0)
         assert err / denom < tol, f"{name}: rel err {err/denom}"
+
+
+@pytest.mark.parametrize("B,N", [(64, 512), (100, 192)])
+def test_fused_linear_backward_bitwise_reproducible(B, N):
+    """Same inputs -> the same gradient bits on every run (the column
+    sums have a fixed order; no float atomics)."""
+    from smartcal_amd.ops.linear import fused_linear
+    torch.manual_seed(0)
+    K = 33
+    x = torch.randn(B, K, device=DEV)
+    params = [torch.randn(N, K, device=DEV) * 0.05,
+              torch.randn(N, device=DEV) * 0.1,
+              torch.rand(N, device=DEV) + 0.5,
+              torch.randn(N, device=DEV) * 0.1]
+    w = torch.randn(B, N, device=DEV)
+    runs = []
+    for _ in range(4):
+        xs = x.clone().requires_grad_(True)
+        ps = [p.clone().requires_grad_(True) for p in params]
+        (fused_linear(xs, *ps, act="elu") * w).sum().backward()
+        runs.append([t.grad.clone() for t in [xs] + ps])
+    for other in runs[1:]:
+        for a, b in zip(runs[0], other):
+            assert torch.equal(a, b)
+
+
+def _fused_linear_case(B, N, K=33):
+    torch.manual_seed(0)
+    x = torch.randn(B, K, device=DEV)
+    params = [torch.randn(N, K, device=DEV) * 0.05,
+              torch.randn(N, device=DEV) * 0.1,
+              torch.rand(N, device=DEV) + 0.5,
+              torch.randn(N, device=DEV) * 0.1]
+    w = torch.randn(B, N, device=DEV)
+    return x, params, w
+
+
+@pytest.mark.parametrize("B,N", [(64, 512), (100, 192)])
+def test_fused_linear_backward_adds_to_existing_grad(B, N):
+    """The backward adds into .grad: a second backward without zeroing
+    leaves every parameter gradient at twice the first (both column-sum
+    paths; x + x is exact in fp32, so the comparison is too)."""
+    from smartcal_amd.ops.linear import fused_linear
+    x, params, w = _fused_linear_case(B, N)
+    ps = [p.clone().requires_grad_(True) for p in params]
+    (fused_linear(x, *ps, act="elu") * w).sum().backward()
+    once = [p.grad.clone() for p in ps]
+    assert all(float(g.abs().max()) > 0 for g in once)
+    (fused_linear(x, *ps, act="elu") * w).sum().backward()
+    for g1, p, name in zip(once, ps, ["dW", "db", "dgamma", "dbeta"]):
+        assert torch.equal(p.grad, g1 + g1), name
+
+
+@pytest.mark.parametrize("B,N", [(64, 512), (100, 192)])
+def test_fused_linear_backward_frozen_params(B, N):
+    """Frozen parameters (the actor phase's critics): dgamma/dbeta sums
+    are skipped, dx is the same as with live parameters and no parameter
+    gets a gradient."""
+    from smartcal_amd.ops.linear import fused_linear
+    x, params, w = _fused_linear_case(B, N)
+    xl = x.clone().requires_grad_(True)
+    live = [p.clone().requires_grad_(True) for p in params]
+    (fused_linear(xl, *live, act="elu") * w).sum().backward()
+    xf = x.clone().requires_grad_(True)
+    frozen = [p.clone() for p in params]
+    (fused_linear(xf, *frozen, act="elu") * w).sum().backward()
+    assert torch.equal(xf.grad, xl.grad)
+    assert all(p.grad is None for p in frozen)
 
 
 def test_mfma_gemms_match_torch():
