@@ -33,6 +33,12 @@ def main():
     ap.add_argument("--seed", default=0, type=int)
     ap.add_argument("--outdir", default=".")
     ap.add_argument("--save-vis", action="store_true")
+    ap.add_argument("--diffuse", action="store_true",
+                    help="add the shapelet diffuse sky (Stokes I, Q, U) "
+                         "to the simulated data")
+    ap.add_argument("--diffuse-flux", default=250.0, type=float)
+    ap.add_argument("--diffuse-beta", default=None, type=float,
+                    help="shapelet scale in rad (default: the model's own)")
     args = ap.parse_args()
     rng = np.random.default_rng(args.seed)
     device = "cuda" if torch.cuda.is_available() else "cpu"
@@ -40,7 +46,9 @@ def main():
 
     t0 = time.time()
     sky, cs_sim, sky_cal, cs_cal, skylmn, rho0, ra0, dec0 = \
-        sim.make_calibration_sky(args.K, rng)
+        sim.make_calibration_sky(args.K, rng, diffuse=args.diffuse,
+                                 diffuse_flux=args.diffuse_flux,
+                                 diffuse_beta=args.diffuse_beta)
     layout = arr.lofar_like_layout(args.stations, rng)
     freqs = np.linspace(115e6, 185e6, args.nf)
     vis = sim.simulate_observation(layout, sky, cs_sim, freqs, ra0, dec0,

@@ -31,6 +31,7 @@ sources = [str(CSRC / f) for f in [
     "attention.hip",
     "cgemm.hip",
     "coherency.hip",
+    "shapelet.hip",
     "hessianres.hip",
     "two_loop.hip",
     "gather_sum.hip",

@@ -50,7 +50,9 @@ class CalibEnv(gymapi.Env):
                  N_stations: int = 26, Nf: int = 8, Ts: int = 2,
                  Tdelta: int = 10, Ninf: int = 128, admm_iter: int = 6,
                  poly_order: int = 3, snr: float = 5.0, device=None,
-                 inf_nfreq: int = 2, seed: int | None = None):
+                 inf_nfreq: int = 2, seed: int | None = None,
+                 diffuse_sky: bool = False, diffuse_flux: float = 250.0,
+                 diffuse_beta: float | None = None):
         super().__init__()
         self.M = M
         self.K = 0
@@ -69,6 +71,10 @@ class CalibEnv(gymapi.Env):
             torch.device("cuda") if torch.cuda.is_available()
             else torch.device("cpu"))
         self.rng = np.random.default_rng(seed)
+        # shapelet diffuse component in the simulated data only
+        # (`radio.sim.make_calibration_sky`)
+        self.diffuse = dict(diffuse=diffuse_sky, diffuse_flux=diffuse_flux,
+                            diffuse_beta=diffuse_beta)
         self.action_space = Box(low=-1.0, high=1.0, shape=(2 * M,))
         self.observation_space = DictSpace({
             "img": Box(low=-HIGH, high=HIGH, shape=(1, Ninf, Ninf)),
@@ -83,7 +89,7 @@ class CalibEnv(gymapi.Env):
 
     def _simulate_episode(self):
         (sky, cs_sim, sky_cal, cs_cal, skylmn, rho0, ra0, dec0) = \
-            rsim.make_calibration_sky(self.K, self.rng)
+            rsim.make_calibration_sky(self.K, self.rng, **self.diffuse)
         layout = arr.lofar_like_layout(self.N, self.rng)
         freqs = np.linspace(115e6, 185e6, self.Nf)
         vis = rsim.simulate_observation(

@@ -77,6 +77,10 @@ extern "C" __global__ void cgemm_nn_bcast_kernel(const float*, const float*,
 extern "C" __global__ void coherency_kernel(const double*, const double*,
                                             const int*, float*, double,
                                             int, int);
+extern "C" __global__ void shapelet_kernel(const double*, const double*,
+                                           const int*, const double*,
+                                           const int*, const int*, float*,
+                                           double, int, int, int, long);
 struct c32h2 { float x, y; };
 extern "C" __global__ void hessianres_kernel(
     const c32h2*, const c32h2*, const c32h2*, const int*, const int*,
@@ -716,6 +720,47 @@ at::Tensor coherency_predict(const at::Tensor& uvw_scaled,
   return C;
 }
 
+// Shapelet sources of all clusters, added into C in one launch.
+// hdr (Ns,12) f64, coff (Ns) i32 offsets into the packed coef (f64),
+// clk (Kc) i32 cluster index per grid row, soff (Kc+1) i32 source ranges.
+void shapelet_predict(at::Tensor C, const at::Tensor& uvw_scaled,
+                      const at::Tensor& hdr, const at::Tensor& coff,
+                      const at::Tensor& coef, const at::Tensor& clk,
+                      const at::Tensor& soff, double fdelta) {
+  TORCH_CHECK(C.is_cuda() && C.scalar_type() == at::kComplexFloat
+              && C.is_contiguous() && C.dim() == 3 && C.size(2) == 4,
+              "C must be contiguous cfloat (K, T, 4) on the GPU");
+  TORCH_CHECK(uvw_scaled.is_cuda()
+              && uvw_scaled.scalar_type() == at::kDouble
+              && uvw_scaled.is_contiguous() && uvw_scaled.dim() == 2
+              && uvw_scaled.size(1) == 3, "uvw must be f64 contiguous (T, 3)");
+  TORCH_CHECK(uvw_scaled.size(0) == C.size(1), "uvw / C sample count");
+  TORCH_CHECK(hdr.is_cuda() && hdr.scalar_type() == at::kDouble
+              && hdr.is_contiguous() && hdr.dim() == 2 && hdr.size(1) == 12,
+              "hdr table must be f64 contiguous (Ns, 12)");
+  TORCH_CHECK(coef.is_cuda() && coef.scalar_type() == at::kDouble
+              && coef.is_contiguous(), "coef must be f64 contiguous");
+  for (const at::Tensor* t : {&coff, &clk, &soff})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kInt
+                && t->is_contiguous(), "index tables must be int32");
+  const int Ns = hdr.size(0);
+  const int Kc = clk.numel();
+  TORCH_CHECK(coff.numel() == Ns && soff.numel() == Kc + 1,
+              "index table sizes");
+  const int K = C.size(0), T = C.size(1);
+  if (Kc == 0 || T == 0) return;
+  dim3 grid((T + 127) / 128, Kc);
+  hipLaunchKernelGGL(shapelet_kernel, grid, dim3(128), 0, stream(),
+                     uvw_scaled.data_ptr<double>(), hdr.data_ptr<double>(),
+                     coff.data_ptr<int>(), coef.data_ptr<double>(),
+                     clk.data_ptr<int>(), soff.data_ptr<int>(),
+                     reinterpret_cast<float*>(C.data_ptr()), fdelta, T, K,
+                     Ns, (long)coef.numel());
+  const hipError_t err = hipGetLastError();
+  TORCH_CHECK(err == hipSuccess, "shapelet_kernel launch: ",
+              hipGetErrorString(err));
+}
+
 // Fused small-sequence attention: O = softmax(Q K^T / sqrt(dh)) V in one
 // launch per call; A (softmax) returned for backward/inspection.
 std::tuple<at::Tensor, at::Tensor> attn_fwd(const at::Tensor& Q,
@@ -787,6 +832,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_bwd", &attn_bwd);
   m.def("cgemm_nn_bcast", &cgemm_nn_bcast);
   m.def("coherency_predict", &coherency_predict);
+  m.def("shapelet_predict", &shapelet_predict);
   m.def("hessianres", &hessianres);
   m.def("two_loop_apply", &two_loop_apply);
   m.def("gather_sum", &gather_sum);

@@ -9,6 +9,14 @@ scaling, bandwidth-smearing sinc and the Gaussian-source envelope.
 Convention: sample axis T = baselines × timeslots in the same ordering as
 the visibility data; output C is (K, T, 4) complex64 with XX = YY = Stokes-I
 coherency, XY = YX = 0, exactly like the reference.
+
+Shapelet sources (names that are keys of ``sky.shapelets``) are kept out
+of the point/Gaussian tables and added on top: a source centred at
+(l0, m0, n0c) contributes ``G = smear(φ0) · e^{iφ0} · F(u, v)`` with
+φ0 = u·l0 + v·m0 + w·n0c, F the closed-form transform of
+`radio.shapelet.shapelet_uv` and smear the point-source sinc at φ0, as
+``XX += (sI+sQ)·G, YY += (sI−sQ)·G, XY = YX += sU·G`` (Stokes at the
+prediction frequency; V, RM and within-source w variation ignored).
 """
 
 from __future__ import annotations
@@ -19,6 +27,7 @@ import numpy as np
 import torch
 
 from .sky import SkyModel, ClusterSet
+from .shapelet import MAX_N0
 
 C_LIGHT = 2.99792458e8
 
@@ -26,9 +35,11 @@ __all__ = ["predict_coherencies", "predict_coherencies_uvw"]
 
 
 def _cluster_source_tensors(sky: SkyModel, cluster, ra0, dec0, freq, device):
-    """Gather per-source tensors for one cluster at ``freq``."""
+    """Gather per-source tensors for one cluster at ``freq`` (point and
+    Gaussian sources; shapelet sources go through `_shapelet_tables`)."""
     idx = sky.index
-    sel = np.asarray([idx[n] for n in cluster.names], dtype=np.int64)
+    sel = np.asarray([idx[n] for n in cluster.names
+                      if n not in sky.shapelets], dtype=np.int64)
     l, m, n = sky.lmn(ra0, dec0)
     lmn = np.stack([l[sel], m[sel], n[sel]], axis=1)          # (S,3)
     flux = sky.flux_at(freq)[sel]                              # (S,)
@@ -38,6 +49,99 @@ def _cluster_source_tensors(sky: SkyModel, cluster, ra0, dec0, freq, device):
             t(sky.eX[sel], torch.float64), t(sky.eY[sel], torch.float64),
             t(sky.eP[sel], torch.float64),
             torch.as_tensor(sky.gaussian[sel], device=device))
+
+
+def _shapelet_tables(sky: SkyModel, clusters: ClusterSet, ra0, dec0, freq):
+    """Per-source tables of all shapelet sources, grouped by cluster, or
+    None when no cluster holds one. Both prediction paths consume these.
+
+    → (hdr (Ns,12) f64, coff (Ns,) i32, coef f64 packed, clk (Kc,) i32,
+    soff (Kc+1,) i32); hdr row = [l0, m0, n0c, sI_f, sQ_f, sU_f, β·a, β·b,
+    cosθ, sinθ, 2πβab, n0]; coff the source's offset into coef; clk the
+    cluster index of each group and soff its source range."""
+    if not sky.shapelets:
+        return None
+    idx = sky.index
+    groups = [(k, [idx[n] for n in cl.names if n in sky.shapelets])
+              for k, cl in enumerate(clusters)]
+    groups = [(k, sel) for k, sel in groups if sel]
+    if not groups:
+        return None
+    l, m, n = sky.lmn(ra0, dec0)
+    hdr, coff, coef, clk, soff = [], [], [], [], [0]
+    ncoef = 0
+    for k, sel in groups:
+        stokes = sky.shapelet_stokes_at(freq, sel)
+        for si, st in zip(sel, stokes):
+            mdl = sky.shapelets[sky.names[si]]
+            if not 1 <= mdl.n0 <= MAX_N0:
+                raise ValueError(
+                    f"shapelet source {sky.names[si]}: n0 = {mdl.n0} "
+                    f"outside the supported range 1..{MAX_N0}")
+            c = np.asarray(mdl.coeff, np.float64).reshape(-1)
+            if c.size != mdl.n0 * mdl.n0:
+                raise ValueError(
+                    f"shapelet source {sky.names[si]}: {c.size} "
+                    f"coefficients for n0 = {mdl.n0}")
+            hdr.append([l[si], m[si], n[si], st[0], st[1], st[2],
+                        mdl.beta * mdl.a, mdl.beta * mdl.b,
+                        math.cos(mdl.theta), math.sin(mdl.theta),
+                        2.0 * math.pi * mdl.beta * mdl.a * mdl.b, mdl.n0])
+            coff.append(ncoef)
+            coef.append(c)
+            ncoef += c.size
+        clk.append(k)
+        soff.append(len(hdr))
+    return (np.asarray(hdr, np.float64), np.asarray(coff, np.int32),
+            np.concatenate(coef), np.asarray(clk, np.int32),
+            np.asarray(soff, np.int32))
+
+
+def _hermite_functions(n0: int, t: torch.Tensor) -> torch.Tensor:
+    """ψ_0..ψ_{n0−1}(t) → (n0, T) f64; torch twin of
+    `radio.shapelet.hermite_functions` (same normalised recurrence)."""
+    rows = [math.pi ** -0.25 * torch.exp(-0.5 * t * t)]
+    if n0 > 1:
+        rows.append(math.sqrt(2.0) * t * rows[0])
+    for n in range(1, n0 - 1):
+        rows.append(t * math.sqrt(2.0 / (n + 1)) * rows[n]
+                    - math.sqrt(n / (n + 1)) * rows[n - 1])
+    return torch.stack(rows)
+
+
+def _add_shapelets_torch(C, u, v, w, tables, fdelta):
+    """Vectorised f64 composition of the shapelet contribution, added
+    into C in place — the CPU path and the oracle of shapelet.hip."""
+    hdr, coff, coef, clk, soff = tables
+    for g, k in enumerate(clk):
+        acc = torch.zeros((3, u.shape[0]), dtype=torch.complex128,
+                          device=u.device)          # XX, YY, XY(=YX)
+        for s in range(soff[g], soff[g + 1]):
+            (l0, m0, n0c, sI, sQ, sU, ba, bb, ct, st, norm,
+             n0) = hdr[s].tolist()
+            n0 = int(n0)
+            pu = _hermite_functions(n0, ba * (ct * u + st * v))
+            pv = _hermite_functions(n0, bb * (-st * u + ct * v))
+            ij = np.arange(n0)
+            cij = coef[coff[s]:coff[s] + n0 * n0].reshape(n0, n0) \
+                * 1j ** ((ij[:, None] + ij[None, :]) % 4)
+            cij = torch.as_tensor(cij, dtype=torch.complex128,
+                                  device=u.device)
+            F = (pu * (cij @ pv.to(torch.complex128))).sum(dim=0)
+            ph = u * l0 + v * m0 + w * n0c
+            amp = torch.full_like(ph, norm)
+            if fdelta is not None:
+                amp = amp * torch.abs(torch.sinc(ph * (0.5 * fdelta / math.pi)))
+            G = torch.polar(amp, ph) * F
+            acc[0] += (sI + sQ) * G
+            acc[1] += (sI - sQ) * G
+            acc[2] += sU * G
+        Ck = C[int(k)].to(torch.complex128)
+        Ck[:, 0] += acc[0]
+        Ck[:, 3] += acc[1]
+        Ck[:, 1] += acc[2]
+        Ck[:, 2] += acc[2]
+        C[int(k)] = Ck.to(torch.complex64)
 
 
 def predict_coherencies_uvw(sky: SkyModel, clusters: ClusterSet,
@@ -51,7 +155,8 @@ def predict_coherencies_uvw(sky: SkyModel, clusters: ClusterSet,
     (the reference hardcodes 180e3 in `calibration_tools.py:380`); None
     disables smearing (matching `skytocoherencies[_torch]`).
     Gaussian sources (name 'G…') get the projected-envelope treatment of
-    `calibration_tools.py:424-448`.
+    `calibration_tools.py:424-448`; shapelet sources (module docstring)
+    are added on top, with mode order n0 ≤ 32 (ValueError beyond).
     """
     device = uvw.device
     T = uvw.shape[0]
@@ -60,14 +165,23 @@ def predict_coherencies_uvw(sky: SkyModel, clusters: ClusterSet,
     v = uvw[:, 1].double() * scale
     w = uvw[:, 2].double() * scale
     fdelta = (smear_bw / freq) if smear_bw is not None else None
+    shp = _shapelet_tables(sky, clusters, ra0, dec0, freq)
 
     from ..ops import use_hip
     if use_hip(uvw.float() if uvw.is_cuda else uvw):
-        # ONE kernel launch for the whole sky (ops/csrc/coherency.hip);
+        # ONE kernel launch for the whole sky (ops/csrc/coherency.hip),
+        # one more for all shapelet sources (ops/csrc/shapelet.hip);
         # the torch composition below is the CPU oracle
-        return _predict_hip(sky, clusters, torch.stack((u, v, w), dim=1)
-                            .contiguous(), freq, ra0, dec0,
-                            fdelta if fdelta is not None else 0.0)
+        uvw_scaled = torch.stack((u, v, w), dim=1).contiguous()
+        C = _predict_hip(sky, clusters, uvw_scaled, freq, ra0, dec0,
+                         fdelta if fdelta is not None else 0.0)
+        if shp is not None:
+            from ..ops import ext
+            ext().shapelet_predict(
+                C, uvw_scaled, *(torch.as_tensor(a, device=device)
+                                 for a in shp),
+                fdelta if fdelta is not None else 0.0)
+        return C
 
     K = len(clusters)
     C = torch.zeros((K, T, 4), dtype=torch.complex64, device=device)
@@ -109,6 +223,8 @@ def predict_coherencies_uvw(sky: SkyModel, clusters: ClusterSet,
             acc = acc + (torch.polar(amp, ph)).sum(dim=1)
         C[ck, :, 0] = acc.to(torch.complex64)
         C[ck, :, 3] = C[ck, :, 0]
+    if shp is not None:
+        _add_shapelets_torch(C, u, v, w, shp, fdelta)
     return C
 
 

@@ -24,6 +24,7 @@ from .sky import SkyModel, ClusterSet, ClusterDef
 from .coherency import predict_coherencies_uvw
 from .solutions import simulate_systematic_errors, solutions_to_J
 from .hessian import baseline_pq
+from .shapelet import generate_random_shapelet_model, load_shapelet_model
 
 __all__ = ["ATEAM", "VisData", "make_calibration_sky", "make_demixing_sky",
            "simulate_observation", "apply_jones", "add_noise", "to_R"]
@@ -89,7 +90,9 @@ def to_R(v: torch.Tensor) -> torch.Tensor:
 
 def make_calibration_sky(K: int, rng: np.random.Generator,
                          nsrc_center: int = 20, nsrc_outlier: int = 8,
-                         n_weak: int = 60, f0: float = 150e6):
+                         n_weak: int = 60, f0: float = 150e6,
+                         diffuse: bool = False, diffuse_flux: float = 250.0,
+                         diffuse_beta: float | None = None):
     """K-direction calibration scenario (center + K−1 outliers + weak
     background), following `simulate.py:6-375`'s statistical recipe at a
     reduced source count (fluxes/spectra/l,m distributions preserved).
@@ -99,6 +102,17 @@ def make_calibration_sky(K: int, rng: np.random.Generator,
     calibration model; skylmn is the (K,5) per-direction averaged
     [id, l, m, sI, sP] DQN metadata; rho0 the analytic flux-scaled ADMM
     rho (`simulate.py` admm_rho0).
+
+    ``diffuse=True`` adds the reference's random diffuse component
+    (`simulate.py:362-375`): shapelet sources ``SLSIRandom``,
+    ``SLSQRandom``, ``SLSURandom`` at the phase centre with
+    ``diffuse_flux`` Jy in Stokes I, Q and U respectively (sp1 = −0.1),
+    each with its own random mode model, in the weak simulation-only
+    cluster. ``diffuse_beta`` overrides the models' scale β: the
+    reference's 0.1–0.2 rad only shows on baselines of a few metres, a
+    smaller β puts structure on the array's real baselines. Their RNG
+    draws come after all others, so the rest of the sky equals the
+    ``diffuse=False`` sky of the same seed.
     """
     ra0, dec0 = 0.0, math.pi / 2.2
     names, ras, decs, sIs, sPs, cl_sim, cl_cal = [], [], [], [], [], [], []
@@ -144,9 +158,23 @@ def make_calibration_sky(K: int, rng: np.random.Generator,
         wk.append(nm); names.append(nm)
         ras.append(ra[i]); decs.append(dec[i])
         sIs.append(0.01 + 0.02 * rng.random()); sPs.append(rng.standard_normal())
+    sQs, sUs, shapelets = [0.0] * len(names), [0.0] * len(names), {}
+    if diffuse:
+        for stokes, nm in enumerate(("SLSIRandom", "SLSQRandom",
+                                     "SLSURandom")):
+            mdl = load_shapelet_model(generate_random_shapelet_model(rng)[0])
+            if diffuse_beta is not None:
+                mdl.beta = float(diffuse_beta)
+            shapelets[nm] = mdl
+            wk.append(nm); names.append(nm)
+            ras.append(ra0); decs.append(dec0); sPs.append(-0.1)
+            flux = [0.0, 0.0, 0.0]
+            flux[stokes] = float(diffuse_flux)
+            sIs.append(flux[0]); sQs.append(flux[1]); sUs.append(flux[2])
     cl_sim.append(ClusterDef(K + 1, 1, wk))
 
-    sky = SkyModel.from_arrays(names, ras, decs, sIs, np.asarray(sPs), f0)
+    sky = SkyModel.from_arrays(names, ras, decs, sIs, np.asarray(sPs), f0,
+                               sQ=sQs, sU=sUs, shapelets=shapelets)
     # analytic rho ∝ flux (simulate.py's admm_rho0 recipe)
     rho0 = fluxes / fluxes.min() * 10.0
     return (sky, ClusterSet(cl_sim), sky, ClusterSet(cl_cal),

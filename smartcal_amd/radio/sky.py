@@ -14,7 +14,9 @@ Sky line format (after the source name; see
     name ra_h ra_m ra_s dec_d dec_m dec_s sI sQ sU sV sp1 sp2 sp3 RM eX eY eP f0
 
 Sources whose name starts with ``G`` are Gaussians (eX/eY/eP used,
-`calibration_tools.py:383-385`).
+`calibration_tools.py:383-385`). A source is a shapelet iff its name is
+a key of ``SkyModel.shapelets`` (the mode file lives outside the sky
+text); only shapelet sources honour sQ/sU in prediction.
 """
 
 from __future__ import annotations
@@ -45,6 +47,10 @@ class SkyModel:
     eY: np.ndarray = field(default_factory=lambda: np.zeros(0))
     eP: np.ndarray = field(default_factory=lambda: np.zeros(0))
     gaussian: np.ndarray = field(default_factory=lambda: np.zeros(0, bool))
+    sQ: np.ndarray = field(default_factory=lambda: np.zeros(0))       # Jy
+    sU: np.ndarray = field(default_factory=lambda: np.zeros(0))       # Jy
+    # name -> radio.shapelet.ShapeletModel for the shapelet sources
+    shapelets: dict = field(default_factory=dict)
 
     def __len__(self):
         return len(self.names)
@@ -55,7 +61,8 @@ class SkyModel:
 
     @staticmethod
     def from_arrays(names, ra, dec, sI, sP=None, f0=1e6, eX=None, eY=None,
-                    eP=None, gaussian=None):
+                    eP=None, gaussian=None, sQ=None, sU=None,
+                    shapelets=None):
         n = len(names)
         sm = SkyModel()
         sm.names = list(names)
@@ -74,14 +81,39 @@ class SkyModel:
         if gaussian is None:
             gaussian = [nm.startswith("G") for nm in sm.names]
         sm.gaussian = np.asarray(gaussian, bool)
+        sm.sQ = np.zeros(n) if sQ is None else np.asarray(sQ, np.float64)
+        sm.sU = np.zeros(n) if sU is None else np.asarray(sU, np.float64)
+        sm.shapelets = dict(shapelets or {})
         return sm
+
+    @property
+    def is_shapelet(self) -> np.ndarray:
+        return np.asarray([n in self.shapelets for n in self.names], bool)
 
     def flux_at(self, freq: float) -> np.ndarray:
         """Extrapolate intensity to ``freq`` with the reference's
-        log-polynomial spectral model (`calibration_tools.py:283-285`)."""
+        log-polynomial spectral model (`calibration_tools.py:283-285`).
+        Shapelet sources (whose sI may be 0) are left out of the log and
+        get 0 here; their fluxes come from `shapelet_stokes_at`."""
+        if self.shapelets:
+            pt = ~self.is_shapelet
+            sub = SkyModel(sI=self.sI[pt], sP=self.sP[pt], f0=self.f0[pt])
+            out = np.zeros(len(self))
+            out[pt] = sub.flux_at(freq)
+            return out
         fr = np.log(freq / self.f0)
         return np.exp(np.log(self.sI) + self.sP[:, 0] * fr
                       + self.sP[:, 1] * fr ** 2 + self.sP[:, 2] * fr ** 3)
+
+    def shapelet_stokes_at(self, freq: float, sel) -> np.ndarray:
+        """(len(sel), 3) Stokes I, Q, U of sources ``sel`` at ``freq``:
+        each scaled by exp(sp1·fr + sp2·fr² + sp3·fr³), fr = ln(f/f0) —
+        no log of the flux, so sI = 0 (pure Q or U sources) is fine."""
+        fr = np.log(freq / self.f0[sel])
+        sp = self.sP[sel]
+        fac = np.exp(sp[:, 0] * fr + sp[:, 1] * fr ** 2 + sp[:, 2] * fr ** 3)
+        return np.stack([self.sI[sel], self.sQ[sel], self.sU[sel]],
+                        axis=1) * fac[:, None]
 
     def lmn(self, ra0: float, dec0: float):
         return radectolm(self.ra, self.dec, ra0, dec0)
@@ -126,20 +158,22 @@ def _data_lines(text: str):
 
 
 def parse_sky_text(text: str) -> SkyModel:
-    names, ra, dec, sI, sP, f0, eX, eY, eP = ([] for _ in range(9))
+    names, ra, dec, sI, sP, f0, eX, eY, eP, sQ, sU = ([] for _ in range(11))
     for cl in _data_lines(text):
         names.append(cl[0])
         s = [float(x) for x in cl[1:]]
         ra.append(hms_to_rad(s[0], s[1], s[2]))
         dec.append(dms_to_rad(s[3], s[4], s[5]))
         sI.append(s[6])
+        sQ.append(s[7])
+        sU.append(s[8])
         sP.append(s[10:13])
         eX.append(s[14])
         eY.append(s[15])
         eP.append(s[16])
         f0.append(s[17])
     return SkyModel.from_arrays(names, ra, dec, sI, np.asarray(sP),
-                                np.asarray(f0), eX, eY, eP)
+                                np.asarray(f0), eX, eY, eP, sQ=sQ, sU=sU)
 
 
 def parse_cluster_text(text: str) -> ClusterSet:
@@ -169,7 +203,8 @@ def write_sky_text(sky: SkyModel) -> str:
         d, dm, ds = rad_to_dec(float(sky.dec[i]))
         sp = sky.sP[i]
         lines.append(
-            f"{nm} {h} {m} {s:.6f} {d} {dm} {ds:.6f} {sky.sI[i]:.6g} 0 0 0 "
+            f"{nm} {h} {m} {s:.6f} {d} {dm} {ds:.6f} {sky.sI[i]:.6g} "
+            f"{sky.sQ[i]:.6g} {sky.sU[i]:.6g} 0 "
             f"{sp[0]:.6g} {sp[1]:.6g} {sp[2]:.6g} 0 {sky.eX[i]:.6g} "
             f"{sky.eY[i]:.6g} {sky.eP[i]:.6g} {sky.f0[i]:.6g}")
     return "\n".join(lines) + "\n"
