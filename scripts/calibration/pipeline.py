@@ -39,6 +39,11 @@ def main():
     ap.add_argument("--diffuse-flux", default=250.0, type=float)
     ap.add_argument("--diffuse-beta", default=None, type=float,
                     help="shapelet scale in rad (default: the model's own)")
+    ap.add_argument("--beam", action="store_true",
+                    help="simulate through the station array-factor beam "
+                         "(calibration stays beamless)")
+    ap.add_argument("--beam-elements", default=48, type=int,
+                    help="elements per station")
     args = ap.parse_args()
     rng = np.random.default_rng(args.seed)
     device = "cuda" if torch.cuda.is_available() else "cpu"
@@ -51,10 +56,17 @@ def main():
                                  diffuse_beta=args.diffuse_beta)
     layout = arr.lofar_like_layout(args.stations, rng)
     freqs = np.linspace(115e6, 185e6, args.nf)
+    elements = None
+    if args.beam:
+        # a generator of its own: rng draws what it draws without --beam
+        elements = arr.station_elements(
+            args.stations, args.beam_elements,
+            np.random.default_rng([args.seed, 0xBEA3]))
     vis = sim.simulate_observation(layout, sky, cs_sim, freqs, ra0, dec0,
                                    args.ts, args.tdelta, snr=5.0,
                                    device=device, rng=rng,
-                                   torch_seed=args.seed)
+                                   torch_seed=args.seed,
+                                   beam_elements=elements)
     print(f"[simulate] {args.stations} stations, {args.nf} sub-bands, "
           f"{vis.S} samples/band: {time.time() - t0:.2f} s")
     if args.save_vis:

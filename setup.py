@@ -32,6 +32,7 @@ sources = [str(CSRC / f) for f in [
     "cgemm.hip",
     "coherency.hip",
     "shapelet.hip",
+    "beam.hip",
     "hessianres.hip",
     "two_loop.hip",
     "gather_sum.hip",

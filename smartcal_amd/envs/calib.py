@@ -52,7 +52,8 @@ class CalibEnv(gymapi.Env):
                  poly_order: int = 3, snr: float = 5.0, device=None,
                  inf_nfreq: int = 2, seed: int | None = None,
                  diffuse_sky: bool = False, diffuse_flux: float = 250.0,
-                 diffuse_beta: float | None = None):
+                 diffuse_beta: float | None = None,
+                 station_beam: bool = False, beam_elements: int = 48):
         super().__init__()
         self.M = M
         self.K = 0
@@ -75,6 +76,13 @@ class CalibEnv(gymapi.Env):
         # (`radio.sim.make_calibration_sky`)
         self.diffuse = dict(diffuse=diffuse_sky, diffuse_flux=diffuse_flux,
                             diffuse_beta=diffuse_beta)
+        # station array-factor beam, likewise in the simulated data only
+        # (the reference simulates with the beam and calibrates without);
+        # element layouts come from a generator of their own, so that
+        # self.rng draws what it draws without a beam
+        self.beam_elements = beam_elements if station_beam else 0
+        self.beam_rng = np.random.default_rng(
+            None if seed is None else [seed, 0xBEA3])
         self.action_space = Box(low=-1.0, high=1.0, shape=(2 * M,))
         self.observation_space = DictSpace({
             "img": Box(low=-HIGH, high=HIGH, shape=(1, Ninf, Ninf)),
@@ -92,10 +100,15 @@ class CalibEnv(gymapi.Env):
             rsim.make_calibration_sky(self.K, self.rng, **self.diffuse)
         layout = arr.lofar_like_layout(self.N, self.rng)
         freqs = np.linspace(115e6, 185e6, self.Nf)
+        elements = None
+        if self.beam_elements:
+            elements = arr.station_elements(self.N, self.beam_elements,
+                                            self.beam_rng)
         vis = rsim.simulate_observation(
             layout, sky, cs_sim, freqs, ra0, dec0, self.Ts, self.Tdelta,
             snr=self.snr, device=self.device, rng=self.rng,
-            torch_seed=int(self.rng.integers(2 ** 31)))
+            torch_seed=int(self.rng.integers(2 ** 31)),
+            beam_elements=elements)
         # cache calibration-model coherencies per freq (constant per episode)
         C = torch.stack([
             predict_coherencies_uvw(sky_cal, cs_cal, vis.uvw, float(f),

@@ -81,6 +81,16 @@ extern "C" __global__ void shapelet_kernel(const double*, const double*,
                                            const int*, const double*,
                                            const int*, const int*, float*,
                                            double, int, int, int, long);
+extern "C" __global__ void shapelet_beam_kernel(
+    const double*, const double*, const int*, const double*, const int*,
+    const int*, float*, double, int, int, int, long, const double*,
+    const int*, const int*, int, int, int, int);
+extern "C" __global__ void station_beam_kernel(const double*, const double*,
+                                               double*, double, int, int,
+                                               int, int);
+extern "C" __global__ void coherency_beam_kernel(
+    const double*, const double*, const int*, const double*, const int*,
+    const int*, float*, double, int, int, int, int, int, int);
 struct c32h2 { float x, y; };
 extern "C" __global__ void hessianres_kernel(
     const c32h2*, const c32h2*, const c32h2*, const int*, const int*,
@@ -720,13 +730,115 @@ at::Tensor coherency_predict(const at::Tensor& uvw_scaled,
   return C;
 }
 
+// Station array-factor table (beam.hip): E (Tt, Sall, N) complex128 for
+// elements elem (Tt, N, Ne, 3) f64 meters and sources lmn (Sall, 3) f64;
+// scale = 2πf/c. One launch.
+at::Tensor station_beam(const at::Tensor& elem, const at::Tensor& lmn,
+                        double scale) {
+  TORCH_CHECK(elem.is_cuda() && elem.scalar_type() == at::kDouble
+              && elem.is_contiguous() && elem.dim() == 4
+              && elem.size(3) == 3,
+              "elem must be f64 contiguous (Tt, N, Ne, 3) on the GPU");
+  TORCH_CHECK(lmn.is_cuda() && lmn.scalar_type() == at::kDouble
+              && lmn.is_contiguous() && lmn.dim() == 2 && lmn.size(1) == 3,
+              "lmn must be f64 contiguous (Sall, 3) on the GPU");
+  const int Tt = elem.size(0), N = elem.size(1), Ne = elem.size(2);
+  const int Sall = lmn.size(0);
+  TORCH_CHECK(Ne >= 1, "a station needs at least one element");
+  TORCH_CHECK(Tt <= 65535 && N <= 65535, "station_beam grid limits: Tt = ",
+              Tt, ", N = ", N);
+  auto E = at::zeros({Tt, Sall, N},
+                     elem.options().dtype(at::kComplexDouble));
+  if (Tt == 0 || N == 0 || Sall == 0) return E;
+  dim3 grid((Sall + 127) / 128, N, Tt);
+  hipLaunchKernelGGL(station_beam_kernel, grid, dim3(128), 0, stream(),
+                     elem.data_ptr<double>(), lmn.data_ptr<double>(),
+                     reinterpret_cast<double*>(E.data_ptr()), scale, Tt, N,
+                     Ne, Sall);
+  const hipError_t err = hipGetLastError();
+  TORCH_CHECK(err == hipSuccess, "station_beam_kernel launch: ",
+              hipGetErrorString(err));
+  return E;
+}
+
+namespace {
+
+// Shared checks of the beam consumers: E (Tt, Sall, N) complex128 and the
+// baseline tables p, q (B) int32 against T = Tt·B samples.
+void check_beam_tables(const at::Tensor& E, const at::Tensor& p,
+                       const at::Tensor& q, int64_t T) {
+  TORCH_CHECK(E.is_cuda() && E.scalar_type() == at::kComplexDouble
+              && E.is_contiguous() && E.dim() == 3,
+              "E must be contiguous cdouble (Tt, Sall, N) on the GPU");
+  for (const at::Tensor* t : {&p, &q})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kInt
+                && t->is_contiguous() && t->dim() == 1,
+                "baseline tables must be int32 (B) on the GPU");
+  TORCH_CHECK(p.numel() == q.numel(), "baseline table sizes");
+  const int64_t Tt = E.size(0), N = E.size(2), B = p.numel();
+  TORCH_CHECK(B == N * (N - 1) / 2, "B = ", B, " baselines for N = ", N,
+              " stations");
+  TORCH_CHECK(T == Tt * B, "T = ", T, " samples, but Tt·B = ", Tt * B);
+}
+
+}  // namespace
+
+// Beam-weighted whole-sky coherency prediction in one launch (beam.hip);
+// rows of src index the source axis of E.
+at::Tensor coherency_beam_predict(const at::Tensor& uvw_scaled,
+                                  const at::Tensor& src,
+                                  const at::Tensor& off, double fdelta,
+                                  const at::Tensor& E, const at::Tensor& p,
+                                  const at::Tensor& q) {
+  TORCH_CHECK(uvw_scaled.is_cuda()
+              && uvw_scaled.scalar_type() == at::kDouble
+              && uvw_scaled.is_contiguous() && uvw_scaled.dim() == 2
+              && uvw_scaled.size(1) == 3, "uvw must be f64 contiguous (T, 3)");
+  TORCH_CHECK(src.is_cuda() && src.scalar_type() == at::kDouble
+              && src.is_contiguous() && src.dim() == 2 && src.size(1) == 11,
+              "src table must be f64 contiguous (S, 11)");
+  TORCH_CHECK(off.is_cuda() && off.scalar_type() == at::kInt
+              && off.is_contiguous() && off.numel() >= 1,
+              "offsets must be int32");
+  const int64_t T = uvw_scaled.size(0);
+  check_beam_tables(E, p, q, T);
+  TORCH_CHECK(src.size(0) <= E.size(1), "E covers ", E.size(1),
+              " sources, src table has ", src.size(0));
+  const int K = off.numel() - 1;
+  const int Tt = E.size(0), Sall = E.size(1), N = E.size(2);
+  const int B = p.numel();
+  TORCH_CHECK(Tt <= 65535 && K <= 65535, "coherency_beam grid limits: Tt = ",
+              Tt, ", K = ", K);
+  auto C = at::zeros({K, T, 4},
+                     uvw_scaled.options().dtype(at::kComplexFloat));
+  if (K == 0 || T == 0) return C;
+  dim3 grid((B + 255) / 256, Tt, K);
+  hipLaunchKernelGGL(coherency_beam_kernel, grid, dim3(256), 0, stream(),
+                     uvw_scaled.data_ptr<double>(), src.data_ptr<double>(),
+                     off.data_ptr<int>(),
+                     reinterpret_cast<const double*>(E.data_ptr()),
+                     p.data_ptr<int>(), q.data_ptr<int>(),
+                     reinterpret_cast<float*>(C.data_ptr()), fdelta, B, Tt,
+                     K, N, (int)src.size(0), Sall);
+  const hipError_t err = hipGetLastError();
+  TORCH_CHECK(err == hipSuccess, "coherency_beam_kernel launch: ",
+              hipGetErrorString(err));
+  return C;
+}
+
 // Shapelet sources of all clusters, added into C in one launch.
 // hdr (Ns,12) f64, coff (Ns) i32 offsets into the packed coef (f64),
 // clk (Kc) i32 cluster index per grid row, soff (Kc+1) i32 source ranges.
+// With a gain table E (Tt, Sall, N) — station_beam, its sources
+// sbase..sbase+Ns the shapelet centres in hdr order — and the baseline
+// tables p, q, every source is weighted by E_p · conj(E_q).
 void shapelet_predict(at::Tensor C, const at::Tensor& uvw_scaled,
                       const at::Tensor& hdr, const at::Tensor& coff,
                       const at::Tensor& coef, const at::Tensor& clk,
-                      const at::Tensor& soff, double fdelta) {
+                      const at::Tensor& soff, double fdelta,
+                      const c10::optional<at::Tensor>& E,
+                      const c10::optional<at::Tensor>& p,
+                      const c10::optional<at::Tensor>& q, int64_t sbase) {
   TORCH_CHECK(C.is_cuda() && C.scalar_type() == at::kComplexFloat
               && C.is_contiguous() && C.dim() == 3 && C.size(2) == 4,
               "C must be contiguous cfloat (K, T, 4) on the GPU");
@@ -748,14 +860,35 @@ void shapelet_predict(at::Tensor C, const at::Tensor& uvw_scaled,
   TORCH_CHECK(coff.numel() == Ns && soff.numel() == Kc + 1,
               "index table sizes");
   const int K = C.size(0), T = C.size(1);
+  const bool beam = E.has_value();
+  TORCH_CHECK(p.has_value() == beam && q.has_value() == beam,
+              "a gain table needs both baseline tables, and they need it");
+  if (beam) {
+    check_beam_tables(*E, *p, *q, T);
+    TORCH_CHECK(sbase >= 0 && sbase + Ns <= E->size(1), "E covers ",
+                E->size(1), " sources, shapelets need ", sbase, "..",
+                sbase + Ns);
+  }
   if (Kc == 0 || T == 0) return;
   dim3 grid((T + 127) / 128, Kc);
-  hipLaunchKernelGGL(shapelet_kernel, grid, dim3(128), 0, stream(),
-                     uvw_scaled.data_ptr<double>(), hdr.data_ptr<double>(),
-                     coff.data_ptr<int>(), coef.data_ptr<double>(),
-                     clk.data_ptr<int>(), soff.data_ptr<int>(),
-                     reinterpret_cast<float*>(C.data_ptr()), fdelta, T, K,
-                     Ns, (long)coef.numel());
+  if (beam)
+    hipLaunchKernelGGL(shapelet_beam_kernel, grid, dim3(128), 0, stream(),
+                       uvw_scaled.data_ptr<double>(), hdr.data_ptr<double>(),
+                       coff.data_ptr<int>(), coef.data_ptr<double>(),
+                       clk.data_ptr<int>(), soff.data_ptr<int>(),
+                       reinterpret_cast<float*>(C.data_ptr()), fdelta, T, K,
+                       Ns, (long)coef.numel(),
+                       reinterpret_cast<const double*>(E->data_ptr()),
+                       p->data_ptr<int>(), q->data_ptr<int>(),
+                       (int)p->numel(), (int)E->size(2), (int)E->size(1),
+                       (int)sbase);
+  else
+    hipLaunchKernelGGL(shapelet_kernel, grid, dim3(128), 0, stream(),
+                       uvw_scaled.data_ptr<double>(), hdr.data_ptr<double>(),
+                       coff.data_ptr<int>(), coef.data_ptr<double>(),
+                       clk.data_ptr<int>(), soff.data_ptr<int>(),
+                       reinterpret_cast<float*>(C.data_ptr()), fdelta, T, K,
+                       Ns, (long)coef.numel());
   const hipError_t err = hipGetLastError();
   TORCH_CHECK(err == hipSuccess, "shapelet_kernel launch: ",
               hipGetErrorString(err));
@@ -832,7 +965,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_bwd", &attn_bwd);
   m.def("cgemm_nn_bcast", &cgemm_nn_bcast);
   m.def("coherency_predict", &coherency_predict);
-  m.def("shapelet_predict", &shapelet_predict);
+  m.def("shapelet_predict", &shapelet_predict, py::arg("C"),
+        py::arg("uvw_scaled"), py::arg("hdr"), py::arg("coff"),
+        py::arg("coef"), py::arg("clk"), py::arg("soff"), py::arg("fdelta"),
+        py::arg("E") = py::none(), py::arg("p") = py::none(),
+        py::arg("q") = py::none(), py::arg("sbase") = 0);
+  m.def("station_beam", &station_beam);
+  m.def("coherency_beam_predict", &coherency_beam_predict);
   m.def("hessianres", &hessianres);
   m.def("two_loop_apply", &two_loop_apply);
   m.def("gather_sum", &gather_sum);

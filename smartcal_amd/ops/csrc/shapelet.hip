@@ -36,7 +36,20 @@
 #define SHP_HDR 12
 #define PI_M14 0.75112554446494248      // π^(−1/4)
 
-extern "C" __global__ __launch_bounds__(SHP_THREADS) void shapelet_kernel(
+// Station-beam gain table of shapelet_beam_kernel (see beam.hip): source s
+// of timeslot t/B on baseline b = t%B = (P[b], Q[b]) is weighted by
+// E[t/B, sbase+s, p] · conj(E[t/B, sbase+s, q]), taken at the source centre.
+struct ShpGain {
+  const double* E;     // (Tt, Sall, N) interleaved complex128
+  const int* P;        // (B)
+  const int* Q;        // (B)
+  int B, N, Sall, sbase;
+};
+
+// BEAM = false is shapelet_kernel as it has always been: `gain` is unused
+// and every beam statement is compiled out.
+template <bool BEAM>
+__device__ __forceinline__ void shapelet_body(
     const double* __restrict__ UVW,   // (T, 3) pre-scaled by 2πf/c
     const double* __restrict__ HDR,   // (Ns, 12)
     const int* __restrict__ COFF,     // (Ns) offsets into COEF
@@ -44,7 +57,7 @@ extern "C" __global__ __launch_bounds__(SHP_THREADS) void shapelet_kernel(
     const int* __restrict__ CLK,      // (Kc) cluster index k in C
     const int* __restrict__ SOFF,     // (Kc+1) source ranges per cluster
     float* __restrict__ C,            // (K, T, 4) interleaved complex64
-    double fdelta, int T, int K, int Ns, long ncoef) {
+    double fdelta, int T, int K, int Ns, long ncoef, const ShpGain& gain) {
   __shared__ double cs[SHP_MAXN * SHP_MAXN];          // 8 KB
   __shared__ double pv[SHP_MAXN * SHP_THREADS];       // 32 KB, [j][thread]
   __shared__ double r1[SHP_MAXN], r2[SHP_MAXN];
@@ -71,6 +84,17 @@ extern "C" __global__ __launch_bounds__(SHP_THREADS) void shapelet_kernel(
   }
   double xx_re = 0.0, xx_im = 0.0, yy_re = 0.0, yy_im = 0.0;
   double xy_re = 0.0, xy_im = 0.0;     // YX = XY
+  const double* ep = nullptr;          // E[t/B, ·, p], E[t/B, ·, q]
+  const double* eq = nullptr;
+  if constexpr (BEAM) {
+    if (t < T) {
+      const int ts = t / gain.B, b = t - ts * gain.B;
+      const double* et = &gain.E[((long)ts * gain.Sall + gain.sbase)
+                                 * gain.N * 2];
+      ep = &et[2 * min(max(gain.P[b], 0), gain.N - 1)];
+      eq = &et[2 * min(max(gain.Q[b], 0), gain.N - 1)];
+    }
+  }
 
   for (int s = s_lo; s < s_hi; ++s) {
     const double* h = &HDR[(long)s * SHP_HDR];
@@ -132,8 +156,18 @@ extern "C" __global__ __launch_bounds__(SHP_THREADS) void shapelet_kernel(
         amp *= (fabs(x) < 1e-12) ? 1.0 : fabs(sin(x) / x);
       }
       const double cp = amp * cos(ph), sp = amp * sin(ph);
-      const double g_re = cp * f_re - sp * f_im;
-      const double g_im = cp * f_im + sp * f_re;
+      double g_re = cp * f_re - sp * f_im;
+      double g_im = cp * f_im + sp * f_re;
+      if constexpr (BEAM) {
+        const long o = (long)s * gain.N * 2;
+        const double pr = ep[o], pi = ep[o + 1];
+        const double qr = eq[o], qi = eq[o + 1];
+        const double b_re = pr * qr + pi * qi;       // E_p · conj(E_q)
+        const double b_im = pi * qr - pr * qi;
+        const double t_re = b_re * g_re - b_im * g_im;
+        g_im = b_re * g_im + b_im * g_re;
+        g_re = t_re;
+      }
       const double fx = h[3] + h[4], fy = h[3] - h[4], fu = h[5];
       xx_re += fx * g_re;  xx_im += fx * g_im;
       yy_re += fy * g_re;  yy_im += fy * g_im;
@@ -152,4 +186,25 @@ extern "C" __global__ __launch_bounds__(SHP_THREADS) void shapelet_kernel(
     o[6] = (float)((double)o[6] + yy_re);     // YY
     o[7] = (float)((double)o[7] + yy_im);
   }
+}
+
+extern "C" __global__ __launch_bounds__(SHP_THREADS) void shapelet_kernel(
+    const double* __restrict__ UVW, const double* __restrict__ HDR,
+    const int* __restrict__ COFF, const double* __restrict__ COEF,
+    const int* __restrict__ CLK, const int* __restrict__ SOFF,
+    float* __restrict__ C, double fdelta, int T, int K, int Ns,
+    long ncoef) {
+  shapelet_body<false>(UVW, HDR, COFF, COEF, CLK, SOFF, C, fdelta, T, K, Ns,
+                       ncoef, ShpGain{});
+}
+
+extern "C" __global__ __launch_bounds__(SHP_THREADS) void shapelet_beam_kernel(
+    const double* __restrict__ UVW, const double* __restrict__ HDR,
+    const int* __restrict__ COFF, const double* __restrict__ COEF,
+    const int* __restrict__ CLK, const int* __restrict__ SOFF,
+    float* __restrict__ C, double fdelta, int T, int K, int Ns, long ncoef,
+    const double* __restrict__ E, const int* __restrict__ P,
+    const int* __restrict__ Q, int B, int N, int Sall, int sbase) {
+  shapelet_body<true>(UVW, HDR, COFF, COEF, CLK, SOFF, C, fdelta, T, K, Ns,
+                      ncoef, ShpGain{E, P, Q, B, N, Sall, sbase});
 }

@@ -17,6 +17,13 @@ of the point/Gaussian tables and added on top: a source centred at
 `radio.shapelet.shapelet_uv` and smear the point-source sinc at φ0, as
 ``XX += (sI+sQ)·G, YY += (sI−sQ)·G, XY = YX += sU·G`` (Stokes at the
 prediction frequency; V, RM and within-source w variation ignored).
+
+Station beam (``beam=``, a `radio.array.StationBeam`): the array factor
+of station p towards source s at timeslot t, steered at the phase centre,
+``E[t,p,s] = (1/Ne)·Σ_e exp(+i·2πf/c·(u_e·l_s + v_e·m_s + w_e·n_s))``,
+weights every source term of baseline (p, q) by ``E[t,p,s]·conj(E[t,q,s])``
+— the station is the average of its elements. A shapelet source takes
+the beam at its centre, on all four correlations.
 """
 
 from __future__ import annotations
@@ -26,12 +33,14 @@ import math
 import numpy as np
 import torch
 
+from .array import StationBeam
+from .hessian import baseline_pq
 from .sky import SkyModel, ClusterSet
 from .shapelet import MAX_N0
 
 C_LIGHT = 2.99792458e8
 
-__all__ = ["predict_coherencies", "predict_coherencies_uvw"]
+__all__ = ["predict_coherencies", "predict_coherencies_uvw", "array_factor"]
 
 
 def _cluster_source_tensors(sky: SkyModel, cluster, ra0, dec0, freq, device):
@@ -109,10 +118,42 @@ def _hermite_functions(n0: int, t: torch.Tensor) -> torch.Tensor:
     return torch.stack(rows)
 
 
-def _add_shapelets_torch(C, u, v, w, tables, fdelta):
+def array_factor(beam: StationBeam, lmn: torch.Tensor,
+                 freq: float) -> torch.Tensor:
+    """Array-factor table E (Tt, N, S) complex128 towards directions
+    ``lmn`` (S, 3) f64 (third component n − 1, as `SkyModel.lmn`), on the
+    device of ``lmn`` — vectorised f64 torch, the oracle of beam.hip."""
+    elem = torch.as_tensor(beam.elem_uvw, dtype=torch.float64,
+                           device=lmn.device) \
+        * (2.0 * math.pi / C_LIGHT * freq)                   # (Tt,N,Ne,3)
+    Tt, N, Ne = elem.shape[:3]
+    S = lmn.shape[0]
+    E = torch.empty((Tt, N, S), dtype=torch.complex128, device=lmn.device)
+    step = max(1, (1 << 22) // max(1, Tt * N * Ne))          # bound memory
+    for s0 in range(0, S, step):
+        ph = elem @ lmn[s0:s0 + step].T                      # (Tt,N,Ne,s)
+        E[:, :, s0:s0 + step] = torch.polar(torch.ones_like(ph),
+                                            ph).mean(dim=2)
+    return E
+
+
+def _beam_gain(E: torch.Tensor, p_idx, q_idx) -> torch.Tensor:
+    """E (Tt, N, s) → per-sample gain E_p·conj(E_q), (Tt·B, s)."""
+    g = E[:, p_idx] * E[:, q_idx].conj()                     # (Tt,B,s)
+    return g.reshape(-1, g.shape[2])
+
+
+def _add_shapelets_torch(C, u, v, w, tables, fdelta, beam=None, freq=None):
     """Vectorised f64 composition of the shapelet contribution, added
-    into C in place — the CPU path and the oracle of shapelet.hip."""
+    into C in place — the CPU path and the oracle of shapelet.hip. With
+    ``beam`` every source is weighted by the array factors at its centre."""
     hdr, coff, coef, clk, soff = tables
+    if beam is not None:
+        p_idx, q_idx = baseline_pq(beam.n_stations, u.device)
+        gain = _beam_gain(
+            array_factor(beam, torch.as_tensor(
+                np.ascontiguousarray(hdr[:, 0:3]), device=u.device), freq),
+            p_idx, q_idx)                                    # (T,Ns)
     for g, k in enumerate(clk):
         acc = torch.zeros((3, u.shape[0]), dtype=torch.complex128,
                           device=u.device)          # XX, YY, XY(=YX)
@@ -133,6 +174,8 @@ def _add_shapelets_torch(C, u, v, w, tables, fdelta):
             if fdelta is not None:
                 amp = amp * torch.abs(torch.sinc(ph * (0.5 * fdelta / math.pi)))
             G = torch.polar(amp, ph) * F
+            if beam is not None:
+                G = G * gain[:, s]
             acc[0] += (sI + sQ) * G
             acc[1] += (sI - sQ) * G
             acc[2] += sU * G
@@ -148,7 +191,8 @@ def predict_coherencies_uvw(sky: SkyModel, clusters: ClusterSet,
                             uvw: torch.Tensor, freq: float,
                             ra0: float, dec0: float,
                             smear_bw: float | None = None,
-                            chunk: int = 512) -> torch.Tensor:
+                            chunk: int = 512,
+                            beam: StationBeam | None = None) -> torch.Tensor:
     """Predict C (K, T, 4) complex64 for raw uvw (T, 3) in meters.
 
     ``smear_bw``: channel bandwidth in Hz for the sinc smearing factor
@@ -157,9 +201,18 @@ def predict_coherencies_uvw(sky: SkyModel, clusters: ClusterSet,
     Gaussian sources (name 'G…') get the projected-envelope treatment of
     `calibration_tools.py:424-448`; shapelet sources (module docstring)
     are added on top, with mode order n0 ≤ 32 (ValueError beyond).
+    ``beam``: weight every source by the station array factors (module
+    docstring); samples must then be ordered s = t·B + b with (p_b, q_b)
+    of `radio.hessian.baseline_pq`, T = Tt·N(N−1)/2 (ValueError if not).
     """
     device = uvw.device
     T = uvw.shape[0]
+    if beam is not None:
+        Tt, N = beam.n_time, beam.n_stations
+        if T != Tt * (N * (N - 1) // 2):
+            raise ValueError(
+                f"uvw has T = {T} samples, the beam needs Tt·N(N−1)/2 = "
+                f"{Tt * (N * (N - 1) // 2)} (Tt = {Tt}, N = {N})")
     scale = 2.0 * math.pi / C_LIGHT * freq
     u = uvw[:, 0].double() * scale
     v = uvw[:, 1].double() * scale
@@ -173,6 +226,10 @@ def predict_coherencies_uvw(sky: SkyModel, clusters: ClusterSet,
         # one more for all shapelet sources (ops/csrc/shapelet.hip);
         # the torch composition below is the CPU oracle
         uvw_scaled = torch.stack((u, v, w), dim=1).contiguous()
+        if beam is not None:
+            return _predict_hip_beam(sky, clusters, uvw_scaled, freq, ra0,
+                                     dec0, fdelta if fdelta is not None
+                                     else 0.0, shp, beam)
         C = _predict_hip(sky, clusters, uvw_scaled, freq, ra0, dec0,
                          fdelta if fdelta is not None else 0.0)
         if shp is not None:
@@ -185,11 +242,15 @@ def predict_coherencies_uvw(sky: SkyModel, clusters: ClusterSet,
 
     K = len(clusters)
     C = torch.zeros((K, T, 4), dtype=torch.complex64, device=device)
+    if beam is not None:
+        p_idx, q_idx = baseline_pq(beam.n_stations, device)
     for ck, cluster in enumerate(clusters):
         lmn, flux, eX2, eY2, eP, gflag = _cluster_source_tensors(
             sky, cluster, ra0, dec0, freq, device)
         S = lmn.shape[0]
         acc = torch.zeros(T, dtype=torch.complex128, device=device)
+        if beam is not None:
+            E = array_factor(beam, lmn, freq)                    # (Tt,N,S)
         for s0 in range(0, S, chunk):
             s1 = min(s0 + chunk, S)
             lm = lmn[s0:s1]                                      # (s,3)
@@ -220,11 +281,19 @@ def predict_coherencies_uvw(sky: SkyModel, clusters: ClusterSet,
                 vvt = 2.0 * eY2[gi] * (spa * uup + cpa * vvp)
                 amp[:, gi] = amp[:, gi] * (0.5 * math.pi
                                            * torch.exp(-(uut * uut + vvt * vvt)))
+            if beam is not None:
+                acc = acc + (torch.polar(amp, ph)
+                             * _beam_gain(E[:, :, s0:s1], p_idx,
+                                          q_idx)).sum(dim=1)
+                continue
             acc = acc + (torch.polar(amp, ph)).sum(dim=1)
         C[ck, :, 0] = acc.to(torch.complex64)
         C[ck, :, 3] = C[ck, :, 0]
     if shp is not None:
-        _add_shapelets_torch(C, u, v, w, shp, fdelta)
+        if beam is not None:
+            _add_shapelets_torch(C, u, v, w, shp, fdelta, beam, freq)
+        else:
+            _add_shapelets_torch(C, u, v, w, shp, fdelta)
     return C
 
 
@@ -236,7 +305,42 @@ def _predict_hip(sky, clusters, uvw_scaled, freq, ra0, dec0, fdelta):
     it collapses to 6 per-source coefficients (see coherency.hip)."""
     from ..ops import ext
 
+    src, off = _source_table(sky, clusters, uvw_scaled.device, freq, ra0,
+                             dec0)
+    return ext().coherency_predict(uvw_scaled, src, off, float(fdelta))
+
+
+def _predict_hip_beam(sky, clusters, uvw_scaled, freq, ra0, dec0, fdelta,
+                      shp, beam):
+    """Beam-weighted prediction on the kernels of ops/csrc/beam.hip: one
+    launch builds E for all point/Gaussian rows and all shapelet centres,
+    one predicts the point/Gaussian coherencies, one adds the shapelets."""
+    from ..ops import ext
+
     device = uvw_scaled.device
+    src, off = _source_table(sky, clusters, device, freq, ra0, dec0)
+    lmn = src[:, 0:3]
+    if shp is not None:
+        lmn = torch.cat((lmn, torch.as_tensor(
+            np.ascontiguousarray(shp[0][:, 0:3]), device=device)))
+    elem = torch.as_tensor(beam.elem_uvw, dtype=torch.float64,
+                           device=device).contiguous()
+    E = ext().station_beam(elem, lmn.contiguous(),
+                           2.0 * math.pi / C_LIGHT * freq)
+    p_idx, q_idx = (i.to(torch.int32)
+                    for i in baseline_pq(beam.n_stations, device))
+    C = ext().coherency_beam_predict(uvw_scaled, src, off, float(fdelta), E,
+                                     p_idx, q_idx)
+    if shp is not None:
+        ext().shapelet_predict(
+            C, uvw_scaled, *(torch.as_tensor(a, device=device) for a in shp),
+            float(fdelta), E, p_idx, q_idx, src.shape[0])
+    return C
+
+
+def _source_table(sky, clusters, device, freq, ra0, dec0):
+    """→ (src (Stot, 11) f64, off (K+1,) i32): the rows of `_predict_hip`
+    for all clusters and the clusters' offsets into them."""
     rows = []
     offs = [0]
     for cluster in clusters:
@@ -267,7 +371,7 @@ def _predict_hip(sky, clusters, uvw_scaled, freq, ra0, dec0, fdelta):
         offs.append(offs[-1] + S)
     src = torch.cat(rows).contiguous()
     off = torch.tensor(offs, dtype=torch.int32, device=device)
-    return ext().coherency_predict(uvw_scaled, src, off, float(fdelta))
+    return src, off
 
 
 def predict_coherencies(sky: SkyModel, clusters: ClusterSet,

@@ -62,6 +62,7 @@ class VisData:
     noise_sigma: float = 0.0
     model: torch.Tensor | None = None     # (Nf, S, 4) noiseless, optional
     J_true: np.ndarray | None = None      # (Nf, K, 2N·Ts, 2) ground truth
+    beam: arr.StationBeam | None = None   # station beam the data went through
 
     @property
     def B(self) -> int:
@@ -280,12 +281,19 @@ def simulate_observation(layout: arr.StationLayout, sky: SkyModel,
                          snr: float = 5.0, dt: float = 10.0,
                          device="cpu", rng: np.random.Generator | None = None,
                          smear_bw: float | None = 180e3,
-                         torch_seed: int | None = None) -> VisData:
+                         torch_seed: int | None = None,
+                         beam_elements: np.ndarray | None = None) -> VisData:
     """Full synthetic observation over Nf frequencies.
 
     The error Jones follow `simulate.py:386-435` (spatially-smooth random
     seeds × quadratic freq polynomial × cosine time modulation), applied
     per solution interval; thermal noise at ``snr``.
+
+    ``beam_elements``: element ENU offsets (N, Ne, 3) of every station
+    (`radio.array.station_elements`); the sky is then seen through the
+    station array-factor beam (the reference simulates with ``-B 2``),
+    kept in ``VisData.beam``. It draws nothing from ``rng`` or the torch
+    generator: the Jones and the noise draw are those of the beamless call.
     """
     rng = rng or np.random.default_rng(0)
     Nf = len(freqs)
@@ -293,6 +301,9 @@ def simulate_observation(layout: arr.StationLayout, sky: SkyModel,
     T = Ts * Tdelta
     times = np.arange(T) * dt
     uvw_t = arr.uvw_synthesis(layout, ra0, dec0, times)     # (T,B,3)
+    beam = None
+    if beam_elements is not None:
+        beam = arr.station_beam(layout, beam_elements, ra0, dec0, times)
     S = T * uvw_t.shape[1]
     uvw = torch.as_tensor(uvw_t.reshape(S, 3), dtype=torch.float32,
                           device=device)
@@ -319,7 +330,7 @@ def simulate_observation(layout: arr.StationLayout, sky: SkyModel,
     sigma = 0.0
     for fi, f in enumerate(freqs):
         C = predict_coherencies_uvw(sky, clusters, uvw, float(f), ra0, dec0,
-                                    smear_bw=smear_bw)
+                                    smear_bw=smear_bw, beam=beam)
         Jf = solutions_to_J(gs[:, :, fi].T, N, Ts)          # (K,2N·Ts,2)
         J_true[fi] = Jf
         J5 = torch.as_tensor(
@@ -330,4 +341,4 @@ def simulate_observation(layout: arr.StationLayout, sky: SkyModel,
         sigma += sig / Nf
     return VisData(uvw=uvw, freqs=np.asarray(freqs, np.float64), data=data,
                    N=N, ra0=ra0, dec0=dec0, Ts=Ts, Tdelta=Tdelta,
-                   noise_sigma=sigma, model=model, J_true=J_true)
+                   noise_sigma=sigma, model=model, J_true=J_true, beam=beam)

@@ -185,13 +185,16 @@ def calibrate(vis: VisData, sky, clusters, rho_spectral,
               alpha: float = 0.0, n_sweeps: int = 3, init_sweeps: int = 6,
               smear_bw: float | None = 180e3,
               C_cache: torch.Tensor | None = None,
-              freq_group: "dist.ProcessGroup | None" = None) -> CalSolution:
+              freq_group: "dist.ProcessGroup | None" = None,
+              beam=None) -> CalSolution:
     """Consensus-ADMM direction-dependent calibration of ``vis``.
 
     rho_spectral: (K,) ADMM regularization per direction (the env action);
     admm_iter: ADMM iterations (the reference's ``-A``);
     poly_order: consensus polynomial terms (``-P``);
-    alpha: federated-averaging / spatial regularization (``-X`` style).
+    alpha: federated-averaging / spatial regularization (``-X`` style);
+    beam: `radio.array.StationBeam` for the model coherencies predicted
+    here (ignored with ``C_cache``); None calibrates without a beam.
 
     When torch.distributed is initialized, each rank is expected to hold
     a disjoint frequency shard in ``vis``; the Z-step all_reduces the
@@ -211,7 +214,8 @@ def calibrate(vis: VisData, sky, clusters, rho_spectral,
     if C_cache is None:
         C = torch.stack([
             predict_coherencies_uvw(sky, clusters, vis.uvw, float(f),
-                                    vis.ra0, vis.dec0, smear_bw=smear_bw)
+                                    vis.ra0, vis.dec0, smear_bw=smear_bw,
+                                    beam=beam)
             for f in vis.freqs])                            # (Nf,K,S,4)
     else:
         C = C_cache
