@@ -18,11 +18,13 @@ extern "C" __global__ void fused_linear_fwd_kernel(
 extern "C" __global__ void ln_act_bwd_kernel(const float*, const float*,
                                              const float*, const float*,
                                              const float*, float*, float*,
-                                             float*, int, int, int, int);
+                                             float*, int, int, int, int,
+                                             int);
 extern "C" __global__ void gemm_f32_nn_kernel(const float*, const float*,
                                               float*, int, int, int);
 extern "C" __global__ void gemm_f32_tn_kernel(const float*, const float*,
-                                              float*, int, int, int, int);
+                                              float*, float*, int, int, int,
+                                              int);
 extern "C" __global__ void colsum_kernel(const float*, float*, int, int,
                                          int);
 extern "C" __global__ void tanh_gauss_fwd_kernel(const float*, const float*,
@@ -163,11 +165,14 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> fused_linear_bwd_dz(
                      gamma ? gamma->data_ptr<float>() : nullptr,
                      dz.data_ptr<float>(), dgamma.data_ptr<float>(),
                      dbeta.data_ptr<float>(), B, N, (int)act,
-                     with_ln ? 1 : 0);
+                     with_ln ? 1 : 0, N);
   return {dz, dgamma, dbeta};
 }
 
-struct ChainArgs {
+// Argument block of mlp_chain_bf16_fwd_kernel, which keeps the plain-chain
+// layout (fused_linear_bf16.hip defines the same struct for itself). The
+// fp32 kernel takes the layer program ChainArgs of common.h.
+struct ChainArgsBf16 {
   const float* W[4];
   const float* bias[4];
   const float* gamma[4];
@@ -181,61 +186,143 @@ struct ChainArgs {
   int L;
   int B;
 };
-extern "C" __global__ void mlp_chain_fwd_kernel(const float*, ChainArgs);
+extern "C" __global__ void mlp_chain_fwd_kernel(ChainArgs);
 extern "C" __global__ void mlp_chain_bf16_fwd_kernel(const float*,
-                                                     ChainArgs);
+                                                     ChainArgsBf16);
 
-// One kernel for a whole Linear(+LN)(+act) chain (≤4 layers, widths ≤512):
-// activations ping-pong in LDS; per-layer y/zhat/rstd still stored for
-// backward. Returns lists [y_l], [zhat_l], [rstd_l].
-std::tuple<std::vector<at::Tensor>, std::vector<at::Tensor>,
-           std::vector<at::Tensor>>
-mlp_chain_fwd(const at::Tensor& x,
-              const std::vector<at::Tensor>& Ws,
-              const std::vector<at::Tensor>& bs,
-              const std::vector<at::Tensor>& gammas,
-              const std::vector<at::Tensor>& betas,
-              const std::vector<int64_t>& acts, bool bf16 = false) {
-  check_f32(x, "x");
-  const int L = (int)Ws.size();
-  TORCH_CHECK(L >= 1 && L <= 4, "chain supports 1..4 layers");
-  const int B = x.size(0);
-  ChainArgs args{};
-  args.L = L;
-  args.B = B;
-  args.dims[0] = x.size(1);
+using OptTensors = std::vector<c10::optional<at::Tensor>>;
+
+struct ChainSaved {
   std::vector<at::Tensor> ys, zhats, rstds;
-  for (int l = 0; l < L; ++l) {
-    check_f32(Ws[l], "W");
-    const int N = Ws[l].size(0);
-    TORCH_CHECK(Ws[l].size(1) == args.dims[l], "chain dim mismatch");
-    TORCH_CHECK(N <= 512 && args.dims[l] <= 512, "chain widths <= 512");
-    args.dims[l + 1] = N;
-    args.W[l] = Ws[l].data_ptr<float>();
-    args.bias[l] = bs[l].defined() ? bs[l].data_ptr<float>() : nullptr;
-    const bool ln = gammas[l].defined();
-    args.with_ln[l] = ln ? 1 : 0;
-    args.gamma[l] = ln ? gammas[l].data_ptr<float>() : nullptr;
-    args.beta[l] = ln ? betas[l].data_ptr<float>() : nullptr;
-    args.act[l] = (int)acts[l];
-    ys.push_back(at::empty({B, N}, x.options()));
-    zhats.push_back(ln ? at::empty({B, N}, x.options())
-                       : at::empty({0}, x.options()));
-    rstds.push_back(ln ? at::empty({B}, x.options())
-                       : at::empty({0}, x.options()));
-    args.Y[l] = ys[l].data_ptr<float>();
-    args.ZHAT[l] = ln ? zhats[l].data_ptr<float>() : nullptr;
-    args.RSTD[l] = ln ? rstds[l].data_ptr<float>() : nullptr;
+};
+
+inline int round_up_64(int v) { return (v + 63) / 64 * 64; }
+
+// Layer l of a chain program: parameters, shape and LDS ranges. With
+// `save` the per-layer y / zhat / rstd that backward needs are allocated
+// and stored; `keep_y` alone allocates y (a final output).
+void chain_set_layer(ChainArgs& a, int l, const at::Tensor& W,
+                     const c10::optional<at::Tensor>& bias,
+                     const c10::optional<at::Tensor>& gamma,
+                     const c10::optional<at::Tensor>& beta, int64_t act,
+                     int src, int src_off, int dst, int dst_off, bool save,
+                     bool keep_y, const at::TensorOptions& opt,
+                     ChainSaved& out) {
+  check_f32(W, "W");
+  const int N = W.size(0), K = W.size(1);
+  const bool ln = gamma.has_value();
+  TORCH_CHECK(!ln || beta.has_value(), "LN requires gamma and beta");
+  TORCH_CHECK(K >= 1 && N >= 1 && K <= 512 && N <= 512,
+              "chain widths must be in 1..512");
+  TORCH_CHECK(src_off >= 0 && dst_off >= 0
+              && src_off + round_up_64(K) <= CHAIN_XMAX
+              && round_up_64(dst_off + N) <= CHAIN_XMAX,
+              "chain layer leaves its LDS buffer");
+  // a layer may read and write one buffer only in disjoint column ranges
+  TORCH_CHECK(src != dst || src_off + round_up_64(K) <= dst_off
+              || round_up_64(dst_off + N) <= src_off,
+              "chain layer reads and writes overlapping LDS columns");
+  if (bias) check_f32(*bias, "bias");
+  if (ln) {
+    check_f32(*gamma, "gamma");
+    check_f32(*beta, "beta");
+    TORCH_CHECK(gamma->numel() == N && beta->numel() == N, "LN size");
   }
+  TORCH_CHECK(!bias || bias->numel() == N, "bias size");
+  a.W[l] = W.data_ptr<float>();
+  a.bias[l] = bias ? bias->data_ptr<float>() : nullptr;
+  a.gamma[l] = ln ? gamma->data_ptr<float>() : nullptr;
+  a.beta[l] = ln ? beta->data_ptr<float>() : nullptr;
+  a.K[l] = K;
+  a.N[l] = N;
+  a.src[l] = src;
+  a.src_off[l] = src_off;
+  a.dst[l] = dst;
+  a.dst_off[l] = dst_off;
+  a.act[l] = (int)act;
+  a.with_ln[l] = ln ? 1 : 0;
+  const int B = a.B;
+  if (save || keep_y) {
+    out.ys.push_back(at::empty({B, N}, opt));
+    a.Y[l] = out.ys.back().data_ptr<float>();
+  }
+  if (save) {
+    out.zhats.push_back(ln ? at::empty({B, N}, opt) : at::empty({0}, opt));
+    out.rstds.push_back(ln ? at::empty({B}, opt) : at::empty({0}, opt));
+    a.ZHAT[l] = ln ? out.zhats.back().data_ptr<float>() : nullptr;
+    a.RSTD[l] = ln ? out.rstds.back().data_ptr<float>() : nullptr;
+  }
+}
+
+void chain_launch(const ChainArgs& args) {
   // dynamic LDS: 2 activation buffers + per-wave W subtiles (16 waves)
   // + row stats — ~139 KB of the 160 KB LDS (one block per CU; only
   // ceil(B/16) blocks exist anyway)
-  const int XP = 577;
+  const int lds_bytes =
+      (2 * 16 * (CHAIN_XMAX + 1) + 16 * 16 * 65 + 16 * 16 * 2 + 16 * 2)
+      * (int)sizeof(float);
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute(
+        reinterpret_cast<const void*>(&mlp_chain_fwd_kernel),
+        hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+    attr_set = true;
+  }
+  if (args.B == 0) return;
+  hipLaunchKernelGGL(mlp_chain_fwd_kernel, dim3((args.B + 15) / 16),
+                     dim3(1024), lds_bytes, stream(), args);
+}
+
+// One kernel for a whole Linear(+LN)(+act) chain (≤4 layers, widths ≤512):
+// activations ping-pong in LDS. Returns lists [y_l], [zhat_l], [rstd_l] for
+// backward; with save == false (nothing will be differentiated) only the
+// last layer's y is allocated and stored: ([y_last], [], []).
+std::tuple<std::vector<at::Tensor>, std::vector<at::Tensor>,
+           std::vector<at::Tensor>>
+mlp_chain_fwd(const at::Tensor& x, const std::vector<at::Tensor>& Ws,
+              const OptTensors& bs, const OptTensors& gammas,
+              const OptTensors& betas, const std::vector<int64_t>& acts,
+              bool bf16, bool save) {
+  check_f32(x, "x");
+  const int L = (int)Ws.size();
+  TORCH_CHECK(L >= 1 && L <= 4, "chain supports 1..4 layers");
+  TORCH_CHECK((int)bs.size() == L && (int)gammas.size() == L
+              && (int)betas.size() == L && (int)acts.size() == L,
+              "chain needs one entry per layer");
+  TORCH_CHECK(x.dim() == 2, "x must be (B, K)");
+  const int B = x.size(0);
   if (bf16) {
+    ChainArgsBf16 args{};
+    args.L = L;
+    args.B = B;
+    args.dims[0] = x.size(1);
+    std::vector<at::Tensor> ys, zhats, rstds;
+    for (int l = 0; l < L; ++l) {
+      check_f32(Ws[l], "W");
+      const int N = Ws[l].size(0);
+      TORCH_CHECK(Ws[l].size(1) == args.dims[l], "chain dim mismatch");
+      TORCH_CHECK(N <= 512 && args.dims[l] <= 512, "chain widths <= 512");
+      args.dims[l + 1] = N;
+      args.W[l] = Ws[l].data_ptr<float>();
+      args.bias[l] = bs[l] ? bs[l]->data_ptr<float>() : nullptr;
+      const bool ln = gammas[l].has_value();
+      args.with_ln[l] = ln ? 1 : 0;
+      args.gamma[l] = ln ? gammas[l]->data_ptr<float>() : nullptr;
+      args.beta[l] = ln ? betas[l]->data_ptr<float>() : nullptr;
+      args.act[l] = (int)acts[l];
+      ys.push_back(at::empty({B, N}, x.options()));
+      zhats.push_back(ln ? at::empty({B, N}, x.options())
+                         : at::empty({0}, x.options()));
+      rstds.push_back(ln ? at::empty({B}, x.options())
+                         : at::empty({0}, x.options()));
+      args.Y[l] = ys[l].data_ptr<float>();
+      args.ZHAT[l] = ln ? zhats[l].data_ptr<float>() : nullptr;
+      args.RSTD[l] = ln ? rstds[l].data_ptr<float>() : nullptr;
+    }
     // bf16 W region: 16 waves x 16 x 72 bf16 rounded up to floats
     const int lds_bytes =
-        (2 * 16 * XP + (16 * 16 * 72 + 1) / 2 + 16 * 16 * 2 + 16 * 2)
-        * (int)sizeof(float);
+        (2 * 16 * (CHAIN_XMAX + 1) + (16 * 16 * 72 + 1) / 2 + 16 * 16 * 2
+         + 16 * 2) * (int)sizeof(float);
     static bool attr_set_b = false;
     if (!attr_set_b) {
       (void)hipFuncSetAttribute(
@@ -248,19 +335,83 @@ mlp_chain_fwd(const at::Tensor& x,
                        x.data_ptr<float>(), args);
     return {ys, zhats, rstds};
   }
-  const int lds_bytes =
-      (2 * 16 * XP + 16 * 16 * 65 + 16 * 16 * 2 + 16 * 2)
-      * (int)sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&mlp_chain_fwd_kernel),
-        hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-    attr_set = true;
+  ChainArgs args{};
+  args.L = L;
+  args.B = B;
+  args.XIN[0] = x.data_ptr<float>();
+  ChainSaved out;
+  int K = x.size(1);
+  for (int l = 0; l < L; ++l) {
+    TORCH_CHECK(Ws[l].dim() == 2 && Ws[l].size(1) == K,
+                "chain dim mismatch");
+    chain_set_layer(args, l, Ws[l], bs[l], gammas[l], betas[l], acts[l],
+                    l & 1, 0, 1 - (l & 1), 0, save, l == L - 1,
+                    x.options(), out);
+    K = Ws[l].size(0);
   }
-  hipLaunchKernelGGL(mlp_chain_fwd_kernel, dim3((B + 15) / 16), dim3(1024),
-                     lds_bytes, stream(), x.data_ptr<float>(), args);
-  return {ys, zhats, rstds};
+  chain_launch(args);
+  return {out.ys, out.zhats, out.rstds};
+}
+
+// The critic (state branch s1, s2; action branch a1, a2; linear head over
+// their concatenation) as ONE chain-kernel launch. Ws/bs/gammas/betas/acts
+// hold s1, s2, a1, a2, head. The branch outputs land side by side in one
+// LDS buffer, which the head reads as its input. Returns q, the
+// concatenated head input zcat (B, N_s2 + N_a2) and the per-layer lists of
+// the four branch layers; with save == false only q is allocated and
+// stored (zcat is empty, the lists too).
+std::tuple<at::Tensor, at::Tensor, std::vector<at::Tensor>,
+           std::vector<at::Tensor>, std::vector<at::Tensor>>
+critic_fwd(const at::Tensor& state, const at::Tensor& action,
+           const std::vector<at::Tensor>& Ws, const OptTensors& bs,
+           const OptTensors& gammas, const OptTensors& betas,
+           const std::vector<int64_t>& acts, bool save) {
+  check_f32(state, "state");
+  check_f32(action, "action");
+  TORCH_CHECK(Ws.size() == 5 && bs.size() == 5 && gammas.size() == 5
+              && betas.size() == 5 && acts.size() == 5,
+              "critic_fwd takes five layers: s1, s2, a1, a2, head");
+  TORCH_CHECK(state.dim() == 2 && action.dim() == 2
+              && state.size(0) == action.size(0),
+              "state and action must be (B, K) with one batch size");
+  for (const auto& W : Ws) TORCH_CHECK(W.dim() == 2, "W must be (N, K)");
+  const int B = state.size(0);
+  const int Ns1 = Ws[0].size(0), Ns2 = Ws[1].size(0);
+  const int Na1 = Ws[2].size(0), Na2 = Ws[3].size(0);
+  TORCH_CHECK(Ws[0].size(1) == state.size(1) && Ws[1].size(1) == Ns1
+              && Ws[2].size(1) == action.size(1) && Ws[3].size(1) == Na1
+              && Ws[4].size(1) == Ns2 + Na2, "critic dim mismatch");
+  TORCH_CHECK(Ns2 + Na2 <= 512, "critic head input <= 512");
+  TORCH_CHECK(!gammas[4].has_value(), "the critic head has no LayerNorm");
+  const int Kpa = round_up_64((int)action.size(1));
+  ChainArgs args{};
+  args.L = 5;
+  args.B = B;
+  args.XIN[0] = state.data_ptr<float>();
+  args.XIN[2] = action.data_ptr<float>();
+  ChainSaved out;
+  const auto opt = state.options();
+  // buffer 0 collects the head input; buffer 1 holds s1's output, then the
+  // staged action (columns 0..Kpa) and a1's output behind it
+  chain_set_layer(args, 0, Ws[0], bs[0], gammas[0], betas[0], acts[0],
+                  0, 0, 1, 0, save, false, opt, out);
+  chain_set_layer(args, 1, Ws[1], bs[1], gammas[1], betas[1], acts[1],
+                  1, 0, 0, 0, save, false, opt, out);
+  chain_set_layer(args, 2, Ws[2], bs[2], gammas[2], betas[2], acts[2],
+                  1, 0, 1, Kpa, save, false, opt, out);
+  chain_set_layer(args, 3, Ws[3], bs[3], gammas[3], betas[3], acts[3],
+                  1, Kpa, 0, Ns2, save, false, opt, out);
+  ChainSaved head;
+  chain_set_layer(args, 4, Ws[4], bs[4], gammas[4], betas[4], acts[4],
+                  0, 0, 1, 0, false, true, opt, head);
+  at::Tensor zcat = at::empty({save ? B : 0, Ns2 + Na2}, opt);
+  if (save) {
+    args.ldc = Ns2 + Na2;
+    args.YC[1] = zcat.data_ptr<float>();
+    args.YC[3] = zcat.data_ptr<float>() + Ns2;
+  }
+  chain_launch(args);
+  return {head.ys[0], zcat, out.ys, out.zhats, out.rstds};
 }
 
 at::Tensor conv2d_k5s2_fwd(const at::Tensor& x, const at::Tensor& W,
@@ -341,13 +492,23 @@ std::tuple<at::Tensor, at::Tensor> als_sweep(
 // (pre-zeroed) flat-grad views the kernel adds its column sums into
 // (fixed summation order, no atomics). Pass None for both when the sums
 // are not wanted (frozen parameters): the kernel then skips them.
+// Without LayerNorm (with_ln false: zhat, rstd and gamma are not read)
+// this is dz = dy * act'(y).
 at::Tensor fused_linear_bwd_dz_into(
     const at::Tensor& dy, const at::Tensor& y, const at::Tensor& zhat,
     const at::Tensor& rstd, const c10::optional<at::Tensor>& gamma,
     int64_t act, bool with_ln, const c10::optional<at::Tensor>& dgamma,
     const c10::optional<at::Tensor>& dbeta) {
-  check_f32(dy, "dy");
+  // dy may be a column slice of a wider row-major matrix (the critic
+  // head's dX, split between the two branches): rows keep unit stride
+  TORCH_CHECK(dy.is_cuda() && dy.scalar_type() == at::kFloat
+              && dy.dim() == 2 && (dy.size(1) == 1 || dy.stride(1) == 1)
+              && dy.stride(0) >= dy.size(1),
+              "dy must be fp32 (B, N) on the GPU with unit column stride");
+  check_f32(y, "y");
   const int B = dy.size(0), N = dy.size(1);
+  TORCH_CHECK(y.dim() == 2 && y.size(0) == B && y.size(1) == N,
+              "dy / y shape mismatch");
   auto dz = at::empty({B, N}, dy.options());
   const bool want_cols = dgamma.has_value();
   TORCH_CHECK(dbeta.has_value() == want_cols,
@@ -366,7 +527,7 @@ at::Tensor fused_linear_bwd_dz_into(
                      dz.data_ptr<float>(),
                      want_cols ? dgamma->data_ptr<float>() : nullptr,
                      want_cols ? dbeta->data_ptr<float>() : nullptr, B, N,
-                     (int)act, with_ln ? 1 : 0);
+                     (int)act, with_ln ? 1 : 0, (int)dy.stride(0));
   return dz;
 }
 
@@ -394,7 +555,7 @@ std::tuple<at::Tensor, at::Tensor> mfma_gemm_tn_bias(const at::Tensor& dz,
   dim3 grid((N + 15) / 16, (K + 63) / 64);
   hipLaunchKernelGGL(gemm_f32_tn_kernel, grid, dim3(256), 0, stream(),
                      dz.data_ptr<float>(), x.data_ptr<float>(),
-                     dW.data_ptr<float>(), N, Bb, K, 0);
+                     dW.data_ptr<float>(), nullptr, N, Bb, K, 0);
   hipLaunchKernelGGL(colsum_kernel, dim3((N + 63) / 64), dim3(256), 0,
                      stream(), dz.data_ptr<float>(), db.data_ptr<float>(),
                      Bb, N, 0);
@@ -402,23 +563,24 @@ std::tuple<at::Tensor, at::Tensor> mfma_gemm_tn_bias(const at::Tensor& dz,
 }
 
 // Direct-accumulate variant: dW/db are views into the (pre-zeroed) flat
-// gradient pool — the GEMM and colsum write with += and the caller skips
-// autograd's per-parameter zero+add kernels entirely.
+// gradient pool — the kernel writes with += and the caller skips
+// autograd's per-parameter zero+add kernels entirely. One launch: the
+// column sums run as an extra grid row of the GEMM kernel.
 void mfma_gemm_tn_bias_into(const at::Tensor& dz, const at::Tensor& x,
                             at::Tensor dW, at::Tensor db) {
   check_f32(dz, "dz");
   check_f32(x, "x");
+  check_f32(dW, "dW");
+  check_f32(db, "db");
   const int Bb = dz.size(0), N = dz.size(1), K = x.size(1);
   TORCH_CHECK(x.size(0) == Bb, "gemm_tn batch mismatch");
-  TORCH_CHECK(dW.is_contiguous() && db.is_contiguous(),
-              "grad views must be contiguous");
-  dim3 grid((N + 15) / 16, (K + 63) / 64);
+  TORCH_CHECK(dW.numel() == (int64_t)N * K && db.numel() == N,
+              "grad views must hold N*K and N elements");
+  dim3 grid((N + 15) / 16, (K + 63) / 64 + 1);
   hipLaunchKernelGGL(gemm_f32_tn_kernel, grid, dim3(256), 0, stream(),
                      dz.data_ptr<float>(), x.data_ptr<float>(),
-                     dW.data_ptr<float>(), N, Bb, K, 1);
-  hipLaunchKernelGGL(colsum_kernel, dim3((N + 63) / 64), dim3(256), 0,
-                     stream(), dz.data_ptr<float>(), db.data_ptr<float>(),
-                     Bb, N, 1);
+                     dW.data_ptr<float>(), db.data_ptr<float>(), N, Bb, K,
+                     1);
 }
 
 // ---- bf16-compute variants (fp32 interfaces, bf16 MFMA inside) ----
@@ -947,7 +1109,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mfma_gemm_tn_bias", &mfma_gemm_tn_bias);
   m.def("mfma_gemm_tn_bias_into", &mfma_gemm_tn_bias_into);
   m.def("fused_linear_bwd_dz_into", &fused_linear_bwd_dz_into);
-  m.def("mlp_chain_fwd", &mlp_chain_fwd);
+  m.def("mlp_chain_fwd", &mlp_chain_fwd, py::arg("x"), py::arg("Ws"),
+        py::arg("bs"), py::arg("gammas"), py::arg("betas"), py::arg("acts"),
+        py::arg("bf16") = false, py::arg("save") = true);
+  m.def("critic_fwd", &critic_fwd, py::arg("state"), py::arg("action"),
+        py::arg("Ws"), py::arg("bs"), py::arg("gammas"), py::arg("betas"),
+        py::arg("acts"), py::arg("save") = true);
   m.def("als_sweep", &als_sweep);
   m.def("conv2d_k5s2_fwd", &conv2d_k5s2_fwd);
   m.def("conv2d_k5s2_bwd", &conv2d_k5s2_bwd);

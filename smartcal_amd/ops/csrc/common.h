@@ -57,6 +57,42 @@ __device__ __forceinline__ float wave_max(float v) {
 // C/D: col = l&15, row = (l>>4)*4 + reg, reg in [0,4).
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
+// Layer program of mlp_chain_fwd_kernel (fused_linear.hip), filled in by
+// bindings.hip. The kernel keeps two LDS activation buffers of 16 rows;
+// layer l reads K[l] columns of buffer src[l] from column src_off[l] and
+// writes its N[l] outputs to buffer dst[l] from column dst_off[l], zeroing
+// up to the next multiple of 64. A plain chain alternates the buffers at
+// offset 0; the critic lands two branches side by side and reads them as
+// one input. XIN[l], if set, is a (B, K[l]) matrix staged into the source
+// range before the layer runs. Every output pointer may be null (nothing
+// stored). YC[l] is a second copy of y into a wider row-major matrix of
+// leading dimension ldc, already offset to its first column.
+#define CHAIN_LAYERS_MAX 6
+struct ChainArgs {
+  const float* W[CHAIN_LAYERS_MAX];
+  const float* bias[CHAIN_LAYERS_MAX];
+  const float* gamma[CHAIN_LAYERS_MAX];
+  const float* beta[CHAIN_LAYERS_MAX];
+  const float* XIN[CHAIN_LAYERS_MAX];
+  float* Y[CHAIN_LAYERS_MAX];
+  float* ZHAT[CHAIN_LAYERS_MAX];
+  float* RSTD[CHAIN_LAYERS_MAX];
+  float* YC[CHAIN_LAYERS_MAX];
+  int K[CHAIN_LAYERS_MAX];
+  int N[CHAIN_LAYERS_MAX];
+  int src[CHAIN_LAYERS_MAX];
+  int src_off[CHAIN_LAYERS_MAX];
+  int dst[CHAIN_LAYERS_MAX];
+  int dst_off[CHAIN_LAYERS_MAX];
+  int act[CHAIN_LAYERS_MAX];
+  int with_ln[CHAIN_LAYERS_MAX];
+  int ldc;
+  int L;
+  int B;
+};
+// widest LDS activation row: 512 columns + one 64-wide tile of zero pad
+#define CHAIN_XMAX 576
+
 // Activation codes shared with python (smartcal_amd/ops/linear.py).
 #define ACT_NONE 0
 #define ACT_ELU 1

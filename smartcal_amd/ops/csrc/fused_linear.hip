@@ -249,7 +249,8 @@ extern "C" __global__ __launch_bounds__(256) void ln_act_bwd_kernel(
     float* __restrict__ DZ,         // (B, N)
     float* __restrict__ DGAMMA,     // (N) accumulated into (+=); may be null
     float* __restrict__ DBETA,      // (N) with DGAMMA
-    int B, int N, int act, int with_ln) {
+    int B, int N, int act, int with_ln,
+    int ldy) {  // row stride of DY: a column slice of a wider matrix is fine
   __shared__ float red[2 * 4];  // per-wave partial sums (m1, m2)
   const int row = blockIdx.x;
   const int tid = threadIdx.x;
@@ -258,7 +259,7 @@ extern "C" __global__ __launch_bounds__(256) void ln_act_bwd_kernel(
   if (!with_ln) {
     for (int c = tid; c < N; c += blockDim.x) {
       const long i = (long)row * N + c;
-      DZ[i] = DY[i] * act_grad_from_y(Yv[i], act);
+      DZ[i] = DY[(long)row * ldy + c] * act_grad_from_y(Yv[i], act);
     }
     return;
   }
@@ -288,7 +289,7 @@ extern "C" __global__ __launch_bounds__(256) void ln_act_bwd_kernel(
       if (c < c1) {
         if (lane < B) {
           const long i = (long)lane * N + c;
-          cdy[k] = DY[i];
+          cdy[k] = DY[(long)lane * ldy + c];
           cy[k] = Yv[i];
           czh[k] = ZHAT[i];
         }
@@ -303,7 +304,8 @@ extern "C" __global__ __launch_bounds__(256) void ln_act_bwd_kernel(
   float m1 = 0.f, m2 = 0.f;
   for (int c = tid; c < N; c += blockDim.x) {
     const long i = (long)row * N + c;
-    const float dh = DY[i] * act_grad_from_y(Yv[i], act);
+    const float dh =
+        DY[(long)row * ldy + c] * act_grad_from_y(Yv[i], act);
     const float zh = ZHAT[i];
     const float dzh = dh * gamma[c];
     m1 += dzh;
@@ -326,7 +328,8 @@ extern "C" __global__ __launch_bounds__(256) void ln_act_bwd_kernel(
   const float rstd = RSTD[row];
   for (int c = tid; c < N; c += blockDim.x) {
     const long i = (long)row * N + c;
-    const float dh = DY[i] * act_grad_from_y(Yv[i], act);
+    const float dh =
+        DY[(long)row * ldy + c] * act_grad_from_y(Yv[i], act);
     const float dzh = dh * gamma[c];
     DZ[i] = rstd * (dzh - M1 - ZHAT[i] * M2);
   }
@@ -351,7 +354,8 @@ extern "C" __global__ __launch_bounds__(256) void ln_act_bwd_kernel(
       float sg = 0.f, sb = 0.f;
       for (int b = lane; b < B; b += 64) {
         const long i = (long)b * N + c;
-        const float dh = DY[i] * act_grad_from_y(Yv[i], act);
+        const float dh =
+            DY[(long)b * ldy + c] * act_grad_from_y(Yv[i], act);
         sg += dh * ZHAT[i];
         sb += dh;
       }
@@ -366,38 +370,33 @@ extern "C" __global__ __launch_bounds__(256) void ln_act_bwd_kernel(
 }
 
 // ---------------------------------------------------------------------------
-// Whole-chain MLP forward: up to CHAIN_MAX Linear(+LN)(+act) layers in ONE
-// kernel. Activations ping-pong between two LDS buffers (no HBM round trip
-// and no kernel launch between layers; the per-k-tile X staging barriers of
-// the single-layer kernel disappear — X is staged once per layer). Each
-// layer still stores y / zhat / rstd to HBM for the (per-layer) backward.
-// Dynamic LDS (~108 KB) => one block per CU, which is fine: the batch-16
+// Whole-chain MLP forward: a program of up to CHAIN_LAYERS_MAX
+// Linear(+LN)(+act) layers in ONE kernel (ChainArgs, common.h). Activations
+// stay in two LDS buffers between layers (no HBM round trip and no kernel
+// launch; the per-k-tile X staging barriers of the single-layer kernel
+// disappear — an input is staged once). Each layer names the buffer and
+// column range it reads and the one it writes, so a plain chain ping-pongs
+// at column 0 and the critic (state branch, action branch, head over their
+// concatenation) runs as one program. Each layer stores y / zhat / rstd to
+// HBM for the (per-layer) backward unless the pointer is null.
+//
+// The W subtiles of the whole program form one sequence (layer, k-tile,
+// column tile); the global loads of the next subtile are always issued
+// before the current subtile's MFMAs, across k-tile and layer boundaries
+// too (the next layer's weights do not depend on the activations). The MFMA
+// order, the tile-to-wave map and the epilogue are those of the single
+// layer kernel, so every output is bit-identical to running the layers
+// one by one.
+// Dynamic LDS (~139 KB) => one block per CU, which is fine: the batch-16
 // row slabs give only ceil(B/16) blocks and the kernel is latency-bound.
 // ---------------------------------------------------------------------------
 
-#define CHAIN_MAX 4
 #define CNW 16          // waves per block (1024 threads): halves the per-wave subtile chain
 #define CNT 3           // max 16-col tiles per wave (16*16*3 = 768 >= 512)
-#define XMAX 576              // max staged width (512 + one BK of zero pad)
-#define XP (XMAX + 1)
-
-struct ChainArgs {
-  const float* W[CHAIN_MAX];
-  const float* bias[CHAIN_MAX];
-  const float* gamma[CHAIN_MAX];
-  const float* beta[CHAIN_MAX];
-  float* Y[CHAIN_MAX];
-  float* ZHAT[CHAIN_MAX];
-  float* RSTD[CHAIN_MAX];
-  int dims[CHAIN_MAX + 1];    // dims[0]=K0 input, dims[l+1]=N_l
-  int act[CHAIN_MAX];
-  int with_ln[CHAIN_MAX];
-  int L;
-  int B;
-};
+#define XP (CHAIN_XMAX + 1)
 
 extern "C" __global__ __launch_bounds__(1024) void mlp_chain_fwd_kernel(
-    const float* __restrict__ X, ChainArgs args) {
+    ChainArgs args) {
   extern __shared__ float smem[];
   float* buf0 = smem;                       // [16][XP]
   float* buf1 = smem + 16 * XP;             // [16][XP]
@@ -412,6 +411,7 @@ extern "C" __global__ __launch_bounds__(1024) void mlp_chain_fwd_kernel(
   const int l4 = lane >> 4;
   const int row0 = blockIdx.x * 16;
   const int B = args.B;
+  const int L = args.L;
 
   const int wc_row[WCH] = {(lane + 0 * WAVE) / (BK / 4),
                            (lane + 1 * WAVE) / (BK / 4),
@@ -423,77 +423,97 @@ extern "C" __global__ __launch_bounds__(1024) void mlp_chain_fwd_kernel(
                          ((lane + 3 * WAVE) % (BK / 4)) * 4};
   float* wsw = ws + wave * 16 * (BK + 1);
 
-  // stage the input (zero-padded to a BK boundary)
-  {
-    const int K0 = args.dims[0];
-    const int Kpad = ((K0 + BK - 1) / BK) * BK;
-    for (int idx = tid; idx < 16 * Kpad; idx += 1024) {
-      const int r = idx / Kpad, c = idx % Kpad;
-      const int gr = row0 + r;
-      buf0[r * XP + c] = (gr < B && c < K0) ? X[(long)gr * K0 + c] : 0.f;
-    }
-  }
-  __syncthreads();
-
-  float* xb = buf0;
-  float* yb = buf1;
-
-  for (int l = 0; l < args.L; ++l) {
-    const int K = args.dims[l];
-    const int N = args.dims[l + 1];
+  // coalesced, guarded float4 load of this wave's W subtile t of k-tile kk
+  // of layer wl into registers (zeros where the wave has no such tile)
+  auto load_wtile = [&](int wl, int kk, int t, float4* vr) {
+    const float* W = args.W[wl];
+    const int K = args.K[wl];
+    const int N = args.N[wl];
     const int ntiles = (N + 15) >> 4;
-    const float* W = args.W[l];
+    const int kmax = min(BK, K - kk);
+    const int ct = wave + CNW * t;
+#pragma unroll
+    for (int i = 0; i < WCH; ++i) {
+      const int col = ct * 16 + wc_row[i];
+      const int k = wc_k[i];
+      float4 v = {0.f, 0.f, 0.f, 0.f};
+      if (ct < ntiles && col < N) {
+        const float* wrow = W + (long)col * K + kk;
+        if (k + 3 < kmax) {
+          v = *reinterpret_cast<const float4*>(wrow + k);
+        } else {
+          if (k + 0 < kmax) v.x = wrow[k + 0];
+          if (k + 1 < kmax) v.y = wrow[k + 1];
+          if (k + 2 < kmax) v.z = wrow[k + 2];
+          if (k + 3 < kmax) v.w = wrow[k + 3];
+        }
+      }
+      vr[i] = v;
+    }
+  };
+  auto write_wtile = [&](const float4* vr) {
+#pragma unroll
+    for (int i = 0; i < WCH; ++i) {
+      const int o = wc_row[i] * (BK + 1) + wc_k[i];
+      wsw[o + 0] = vr[i].x;
+      wsw[o + 1] = vr[i].y;
+      wsw[o + 2] = vr[i].z;
+      wsw[o + 3] = vr[i].w;
+    }
+  };
+
+  // the one W subtile in flight: loaded one step ahead of its MFMAs
+  float4 wr[WCH];
+  load_wtile(0, 0, 0, wr);
+
+  for (int l = 0; l < L; ++l) {
+    const int K = args.K[l];
+    const int N = args.N[l];
+    const int ntiles = (N + 15) >> 4;
     const int with_ln = args.with_ln[l];
+    float* xb = (args.src[l] ? buf1 : buf0) + args.src_off[l];
+    float* yb = (args.dst[l] ? buf1 : buf0) + args.dst_off[l];
+
+    // a wave with no column tile in this layer issues no step below:
+    // it fetches its first subtile of the next layer now
+    if (wave >= ntiles && l + 1 < L) load_wtile(l + 1, 0, 0, wr);
+
+    // stage an external input (zero-padded to a BK boundary)
+    if (const float* X = args.XIN[l]) {
+      const int Kpad = ((K + BK - 1) / BK) * BK;
+      for (int idx = tid; idx < 16 * Kpad; idx += 1024) {
+        const int r = idx / Kpad, c = idx % Kpad;
+        const int gr = row0 + r;
+        xb[r * XP + c] = (gr < B && c < K) ? X[(long)gr * K + c] : 0.f;
+      }
+      __syncthreads();
+    }
 
     f32x4 acc[CNT];
 #pragma unroll
     for (int t = 0; t < CNT; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
     for (int kk = 0; kk < K; kk += BK) {
-      const int kmax = min(BK, K - kk);
-      auto load_wtile = [&](int t, float4* vr) {
-#pragma unroll
-        for (int i = 0; i < WCH; ++i) {
-          const int ct = wave + CNW * t;
-          const int col = ct * 16 + wc_row[i];
-          const int k = wc_k[i];
-          float4 v = {0.f, 0.f, 0.f, 0.f};
-          if (ct < ntiles && col < N) {
-            const float* wrow = W + (long)col * K + kk;
-            if (k + 3 < kmax) {
-              v = *reinterpret_cast<const float4*>(wrow + k);
-            } else {
-              if (k + 0 < kmax) v.x = wrow[k + 0];
-              if (k + 1 < kmax) v.y = wrow[k + 1];
-              if (k + 2 < kmax) v.z = wrow[k + 2];
-              if (k + 3 < kmax) v.w = wrow[k + 3];
-            }
-          }
-          vr[i] = v;
-        }
-      };
-      auto write_wtile = [&](const float4* vr) {
-#pragma unroll
-        for (int i = 0; i < WCH; ++i) {
-          const int o = wc_row[i] * (BK + 1) + wc_k[i];
-          wsw[o + 0] = vr[i].x;
-          wsw[o + 1] = vr[i].y;
-          wsw[o + 2] = vr[i].z;
-          wsw[o + 3] = vr[i].w;
-        }
-      };
-      float4 wa[WCH], wb[WCH];
-      load_wtile(0, wa);
 #pragma unroll
       for (int t = 0; t < CNT; ++t) {
         const int ct = wave + CNW * t;
         if (ct >= ntiles) break;
-        if (t % 2 == 0) {
-          write_wtile(wa);
-          if (t + 1 < CNT) load_wtile(t + 1, wb);
-        } else {
-          write_wtile(wb);
-          if (t + 1 < CNT) load_wtile(t + 1, wa);
+        // write subtile t to LDS, issue the next subtile's global loads
+        // (next column tile, else next k-tile, else next layer), run
+        // subtile t's MFMAs: the global latency hides under the MFMA + ds
+        // traffic (T14)
+        write_wtile(wr);
+        {
+          int nl = l, nkk = kk, nt = t + 1;
+          if (nt >= CNT || wave + CNW * nt >= ntiles) {
+            nt = 0;
+            nkk = kk + BK;
+            if (nkk >= K) {
+              nkk = 0;
+              nl = l + 1;
+            }
+          }
+          if (nl < L) load_wtile(nl, nkk, nt, wr);
         }
         // front-load all LDS operand reads (see single-layer kernel note)
         float ar[BK / 4], br[BK / 4];
@@ -516,10 +536,16 @@ extern "C" __global__ __launch_bounds__(1024) void mlp_chain_fwd_kernel(
       }
     }
 
-    // ---- epilogue: bias + LN + act; write HBM + the LDS ping buffer ----
+    // ---- epilogue: bias + LN + act; write HBM + the LDS destination ----
     const float* bias = args.bias[l];
     const float* gamma = args.gamma[l];
     const float* beta = args.beta[l];
+    float* Yg = args.Y[l];
+    float* ZHg = args.ZHAT[l];
+    float* RSg = args.RSTD[l];
+    float* YCg = args.YC[l];
+    const int ldc = args.ldc;
+    const int act = args.act[l];
     float zrow[CNT][4];
     float psum[4] = {0.f, 0.f, 0.f, 0.f}, psq[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -563,14 +589,15 @@ extern "C" __global__ __launch_bounds__(1024) void mlp_chain_fwd_kernel(
         rowmv[tid * 2 + 0] = mean;
         rowmv[tid * 2 + 1] = rstd;
         const int grow = row0 + tid;
-        if (grow < B && args.RSTD[l]) args.RSTD[l][grow] = rstd;
+        if (grow < B && RSg) RSg[grow] = rstd;
       }
       __syncthreads();
     }
-    // zero the pad region of the ping buffer for the next layer's reads
+    // zero the pad columns after the outputs, up to the BK boundary, for
+    // the reads of the layer that consumes them
     {
-      const int Npad = ((N + BK - 1) / BK) * BK;
-      const int padw = Npad - N;
+      const int endc = args.dst_off[l] + N;
+      const int padw = ((endc + BK - 1) / BK) * BK - endc;
       if (padw > 0) {
         for (int idx = tid; idx < 16 * padw; idx += 1024) {
           const int r = idx / padw, c = N + idx % padw;
@@ -596,17 +623,19 @@ extern "C" __global__ __launch_bounds__(1024) void mlp_chain_fwd_kernel(
           float out;
           if (with_ln) {
             const float zh = (z - mean) * rstd;
-            if (grow < B) args.ZHAT[l][(long)grow * N + col] = zh;
-            out = apply_act(gamma[col] * zh + beta[col], args.act[l]);
+            if (grow < B && ZHg) ZHg[(long)grow * N + col] = zh;
+            out = apply_act(gamma[col] * zh + beta[col], act);
           } else {
-            out = apply_act(z, args.act[l]);
+            out = apply_act(z, act);
           }
           yb[lrow * XP + col] = out;
-          if (grow < B) args.Y[l][(long)grow * N + col] = out;
+          if (grow < B) {
+            if (Yg) Yg[(long)grow * N + col] = out;
+            if (YCg) YCg[(long)grow * ldc + col] = out;
+          }
         }
       }
     }
     __syncthreads();
-    float* tmp = xb; xb = yb; yb = tmp;
   }
 }

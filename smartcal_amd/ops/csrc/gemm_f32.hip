@@ -84,17 +84,50 @@ extern "C" __global__ __launch_bounds__(256) void gemm_f32_nn_kernel(
   }
 }
 
+// Column sums of DZ (B, N) for the 64 columns of block blk: 256 threads
+// cover 64 columns x 4 row-stripes (coalesced: consecutive threads ->
+// consecutive columns), combined through LDS (red: 4*64 floats).
+__device__ __forceinline__ void colsum_block(const float* __restrict__ DZ,
+                                             float* __restrict__ OUT, int B,
+                                             int N, int accumulate, int blk,
+                                             float* red) {
+  const int c = blk * 64 + (threadIdx.x & 63);
+  const int stripe = threadIdx.x >> 6;
+  float s = 0.f;
+  if (c < N)
+    for (int r = stripe; r < B; r += 4) s += DZ[(long)r * N + c];
+  red[stripe * 64 + (threadIdx.x & 63)] = s;
+  __syncthreads();
+  if (threadIdx.x < 64 && c < N) {
+    const float s4 = red[threadIdx.x] + red[64 + threadIdx.x] +
+                     red[128 + threadIdx.x] + red[192 + threadIdx.x];
+    OUT[c] = accumulate ? OUT[c] + s4 : s4;
+  }
+}
+
 // C (M,N) = A^T @ B with A (K,M), B (K,N) row-major (e.g. dW = dZ^T @ X).
 // accumulate: C += result (direct-accumulate into a pre-zeroed flat grad
 // pool — removes the separate autograd add/zero kernels per parameter).
+//
+// CS non-null: the launch carries one extra grid row (blockIdx.y ==
+// gridDim.y - 1) whose first ceil(M/64) blocks write the column sums of A
+// (the bias gradient, db = col-sum(dZ)) to CS through colsum_block, instead
+// of a colsum_kernel launch behind the GEMM.
 extern "C" __global__ __launch_bounds__(256) void gemm_f32_tn_kernel(
     const float* __restrict__ A, const float* __restrict__ B,
-    float* __restrict__ C, int M, int K, int N, int accumulate) {
+    float* __restrict__ C, float* __restrict__ CS, int M, int K, int N,
+    int accumulate) {
   const int tid = threadIdx.x;
   const int wave = tid >> 6;
   const int lane = tid & 63;
   const int l15 = lane & 15;
   const int l4 = lane >> 4;
+  if (CS && blockIdx.y == gridDim.y - 1) {  // block-uniform
+    __shared__ float red[4 * 64];
+    if ((int)blockIdx.x * 64 < M)
+      colsum_block(A, CS, K, M, accumulate, blockIdx.x, red);
+    return;
+  }
   const int row0 = blockIdx.x * 16;
   const int col0 = (blockIdx.y * 4 + wave) * 16;
   if (col0 >= N) return;
@@ -128,23 +161,11 @@ extern "C" __global__ __launch_bounds__(256) void gemm_f32_tn_kernel(
   }
 }
 
-// db (N) = column sums of DZ (B, N). Block = 256 threads covering 64
-// columns x 4 row-stripes (coalesced: consecutive threads -> consecutive
-// columns), combined through LDS. accumulate: OUT += sums.
+// db (N) = column sums of DZ (B, N), one colsum_block per 64 columns.
+// accumulate: OUT += sums.
 extern "C" __global__ __launch_bounds__(256) void colsum_kernel(
     const float* __restrict__ DZ, float* __restrict__ OUT, int B, int N,
     int accumulate) {
   __shared__ float red[4 * 64];
-  const int c = blockIdx.x * 64 + (threadIdx.x & 63);
-  const int stripe = threadIdx.x >> 6;
-  float s = 0.f;
-  if (c < N)
-    for (int r = stripe; r < B; r += 4) s += DZ[(long)r * N + c];
-  red[stripe * 64 + (threadIdx.x & 63)] = s;
-  __syncthreads();
-  if (threadIdx.x < 64 && c < N) {
-    const float s4 = red[threadIdx.x] + red[64 + threadIdx.x] +
-                     red[128 + threadIdx.x] + red[192 + threadIdx.x];
-    OUT[c] = accumulate ? OUT[c] + s4 : s4;
-  }
+  colsum_block(DZ, OUT, B, N, accumulate, blockIdx.x, red);
 }

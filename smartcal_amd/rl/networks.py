@@ -10,6 +10,10 @@ Architectures mirror the reference agents' nets:
 * Critic: state branch in->512->256, action branch A->128->64, concat,
   linear head to 1 (reference ``enet_sac.py:352-394``).
 
+On the HIP fp32 path an actor forward (trunk and head) and a critic forward
+(both branches and the head) are ONE chain-kernel launch each; CPU and bf16
+compute compose the layers.
+
 Weight init follows the reference's ``init_layer`` (uniform +-1/sqrt(fan),
 0.003 for heads, ``enet_sac.py:18-22``).
 """
@@ -19,11 +23,30 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from ..ops.linear import FusedLinear, fused_linear, fused_chain
+from ..ops import use_hip
+from ..ops.linear import (FusedLinear, fused_linear, fused_chain,
+                          fused_critic, get_compute_dtype)
 from ..ops.sampling import tanh_gauss_sample
 
 LOGSIG_MIN = -20.0
 LOGSIG_MAX = 2.0
+
+# Tests only: True forces the composed forwards (trunk chain + separate head
+# launch; state chain + action chain + cat + head) instead of the one-kernel
+# ones, so both can be compared inside one build. Never set in production.
+FORCE_COMPOSITION = False
+
+
+def _one_kernel() -> bool:
+    """The head folds into the trunk's chain kernel (fp32 compute only;
+    bf16 keeps the composition)."""
+    return not FORCE_COMPOSITION and get_compute_dtype() == "fp32"
+
+
+def _actor_out(net, x: torch.Tensor) -> torch.Tensor:
+    if _one_kernel():
+        return fused_chain(x, (net.l1, net.l2, net.l3, net.head))
+    return net.head(fused_chain(x, (net.l1, net.l2, net.l3)))
 
 
 class SACActorMLP(nn.Module):
@@ -38,9 +61,8 @@ class SACActorMLP(nn.Module):
                                 init_scale=0.003)
 
     def forward(self, x: torch.Tensor):
-        # whole hidden stack as ONE chain kernel (activations in LDS)
-        h = fused_chain(x, (self.l1, self.l2, self.l3))
-        out = self.head(h)
+        # hidden stack and head as ONE chain kernel (activations in LDS)
+        out = _actor_out(self, x)
         mu = out[..., :self.n_actions]
         logsigma = out[..., self.n_actions:].clamp(LOGSIG_MIN, LOGSIG_MAX)
         return mu, logsigma
@@ -66,7 +88,7 @@ class DeterministicActorMLP(nn.Module):
                                 init_scale=0.003)
 
     def forward(self, x: torch.Tensor):
-        return self.head(fused_chain(x, (self.l1, self.l2, self.l3)))
+        return _actor_out(self, x)
 
 
 class CriticMLP(nn.Module):
@@ -80,6 +102,9 @@ class CriticMLP(nn.Module):
                                 init_scale=0.003)
 
     def forward(self, state: torch.Tensor, action: torch.Tensor):
+        if _one_kernel() and use_hip(state):
+            return fused_critic(state, action, (self.s1, self.s2, self.a1,
+                                                self.a2, self.head))
         x = fused_chain(state, (self.s1, self.s2))
         y = fused_chain(action, (self.a1, self.a2))
         z = torch.cat((x, y), dim=-1)
