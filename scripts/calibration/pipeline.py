@@ -44,6 +44,9 @@ def main():
                          "(calibration stays beamless)")
     ap.add_argument("--beam-elements", default=48, type=int,
                     help="elements per station")
+    ap.add_argument("--imager", default="grid", choices=["grid", "dft"],
+                    help="grid: nearest-cell gridder + FFT; dft: exact "
+                         "direct Fourier sum with the w-term")
     args = ap.parse_args()
     rng = np.random.default_rng(args.seed)
     device = "cuda" if torch.cuda.is_available() else "cpu"
@@ -83,13 +86,15 @@ def main():
 
     t0 = time.time()
     imgs_d, imgs_r, imgs_i = [], [], []
+    vals_i = []
     f0 = float(np.mean(vis.freqs))
     for fi in range(args.nf):
         f = float(vis.freqs[fi])
         sI_d = 0.5 * (vis.data[fi][:, 0] + vis.data[fi][:, 3])
         sI_r = 0.5 * (sol.residual[fi][:, 0] + sol.residual[fi][:, 3])
-        imgs_d.append(imaging.dirty_image(vis.uvw, sI_d, f, 128))
-        imgs_r.append(imaging.dirty_image(vis.uvw, sI_r, f, 128))
+        if args.imager == "grid":
+            imgs_d.append(imaging.dirty_image(vis.uvw, sI_d, f, 128))
+            imgs_r.append(imaging.dirty_image(vis.uvw, sI_r, f, 128))
         C = predict_coherencies_uvw(sky_cal, cs_cal, vis.uvw, f, ra0, dec0,
                                     smear_bw=180e3)
         Hadd = influence.hadd_for(args.K, vis.N, args.poly, vis.freqs, f0,
@@ -98,7 +103,20 @@ def main():
                                           sol.J_ref_layout(fi), vis.N,
                                           vis.Tdelta, Hadd)
         sI_i = 0.5 * (vals[:, 0] + vals[:, 3])
-        imgs_i.append(imaging.dirty_image(vis.uvw, sI_i, f, 128))
+        if args.imager == "grid":
+            imgs_i.append(imaging.dirty_image(vis.uvw, sI_i, f, 128))
+        else:
+            vals_i.append(sI_i)
+    if args.imager == "dft":
+        # all bands at once: data + residual maps, then the influence maps
+        sI = torch.stack([
+            0.5 * (vis.data[:, :, 0] + vis.data[:, :, 3]),
+            0.5 * (sol.residual[:, :, 0] + sol.residual[:, :, 3])], dim=1)
+        cube = imaging.dft_image_cube(vis.uvw, sI, vis.freqs, 128)
+        cube_i = imaging.dft_image_cube(
+            vis.uvw, torch.stack(vals_i)[:, None], vis.freqs, 128)
+        imgs_d, imgs_r = list(cube[:, 0]), list(cube[:, 1])
+        imgs_i = list(cube_i[:, 0])
     data_img = imaging.weighted_mean_image(imgs_d, vis.freqs)
     res_img = imaging.weighted_mean_image(imgs_r, vis.freqs)
     inf_img = imaging.weighted_mean_image(imgs_i, vis.freqs)

@@ -53,8 +53,19 @@ class CalibEnv(gymapi.Env):
                  inf_nfreq: int = 2, seed: int | None = None,
                  diffuse_sky: bool = False, diffuse_flux: float = 250.0,
                  diffuse_beta: float | None = None,
-                 station_beam: bool = False, beam_elements: int = 48):
+                 station_beam: bool = False, beam_elements: int = 48,
+                 imager: str = "grid", image_fov: float | None = None,
+                 image_wterm: bool = True):
         super().__init__()
+        if imager not in ("grid", "dft"):
+            raise ValueError(f"imager must be 'grid' or 'dft', got "
+                             f"{imager!r}")
+        # "grid": nearest-cell gridder + FFT (`imaging.dirty_image`);
+        # "dft": exact direct Fourier sum with the w-term
+        # (`imaging.dft_image_cube`), image_fov / image_wterm apply to it
+        self.imager = imager
+        self.image_fov = image_fov
+        self.image_wterm = image_wterm
         self.M = M
         self.K = 0
         self.provide_hint = provide_hint
@@ -129,25 +140,39 @@ class CalibEnv(gymapi.Env):
             C_cache=sc["C"])
         # data / residual dirty images (σ over the mean image, à la
         # calmean + fits std in `calibenv.py:148-158`)
-        imgs_d, imgs_r, imgs_i = [], [], []
         inf_idx = np.linspace(0, self.Nf - 1, self.inf_nfreq).astype(int)
         f0 = float(np.mean(vis.freqs))
-        for fi in range(self.Nf):
-            f = float(vis.freqs[fi])
-            sI_d = 0.5 * (vis.data[fi][:, 0] + vis.data[fi][:, 3])
-            sI_r = 0.5 * (sol.residual[fi][:, 0] + sol.residual[fi][:, 3])
-            imgs_d.append(rimg.dirty_image(vis.uvw, sI_d, f, self.Ninf))
-            imgs_r.append(rimg.dirty_image(vis.uvw, sI_r, f, self.Ninf))
+        sI_d = [0.5 * (vis.data[fi][:, 0] + vis.data[fi][:, 3])
+                for fi in range(self.Nf)]
+        sI_r = [0.5 * (sol.residual[fi][:, 0] + sol.residual[fi][:, 3])
+                for fi in range(self.Nf)]
+        sI_i = []
         for fi in inf_idx:
-            f = float(vis.freqs[fi])
             Hadd = rinf.hadd_for(K, vis.N, self.poly_order, vis.freqs, f0,
                                  int(fi), self.rho_spectral[:K],
                                  self.rho_spatial[:K], self.device)
             vals = rinf.influence_values(sol.residual[fi], sc["C"][fi],
                                          sol.J_ref_layout(int(fi)), vis.N,
                                          vis.Tdelta, Hadd)
-            sI_i = 0.5 * (vals[:, 0] + vals[:, 3])
-            imgs_i.append(rimg.dirty_image(vis.uvw, sI_i, f, self.Ninf))
+            sI_i.append(0.5 * (vals[:, 0] + vals[:, 3]))
+        if self.imager == "dft":
+            # two launches: data + residual maps of all bands (M = 2),
+            # then the influence maps of the inf_nfreq bands
+            kw = dict(npix=self.Ninf, fov=self.image_fov,
+                      wterm=self.image_wterm)
+            cube = rimg.dft_image_cube(
+                vis.uvw, torch.stack([torch.stack(sI_d), torch.stack(sI_r)],
+                                     dim=1), vis.freqs, **kw)
+            cube_i = rimg.dft_image_cube(vis.uvw, torch.stack(sI_i)[:, None],
+                                         vis.freqs[inf_idx], **kw)
+            imgs_d, imgs_r = list(cube[:, 0]), list(cube[:, 1])
+            imgs_i = list(cube_i[:, 0])
+        else:
+            def grid(maps, fs):
+                return [rimg.dirty_image(vis.uvw, sI, float(f), self.Ninf)
+                        for sI, f in zip(maps, fs)]
+            imgs_d, imgs_r = grid(sI_d, vis.freqs), grid(sI_r, vis.freqs)
+            imgs_i = grid(sI_i, vis.freqs[inf_idx])
         data_img = rimg.weighted_mean_image(imgs_d, vis.freqs)
         res_img = rimg.weighted_mean_image(imgs_r, vis.freqs)
         inf_img = rimg.weighted_mean_image(imgs_i, vis.freqs[inf_idx])

@@ -45,8 +45,14 @@ class DemixingEnv(gymapi.Env):
                  Npix: int = 1024, Tdelta: int = 10, provide_hint=False,
                  provide_influence=False, N_stations: int = 26,
                  Ts: int = 2, poly_order: int = 2, device=None,
-                 seed: int | None = None):
+                 seed: int | None = None, imager: str = "grid"):
         super().__init__()
+        if imager not in ("grid", "dft"):
+            raise ValueError(f"imager must be 'grid' or 'dft', got "
+                             f"{imager!r}")
+        # imager of the Ninf influence map only: "grid" = nearest-cell
+        # gridder, "dft" = exact direct Fourier sum (`imaging.dft_image`)
+        self.imager = imager
         self.K = K
         self.Nf = Nf
         self.Ninf = Ninf
@@ -132,7 +138,8 @@ class DemixingEnv(gymapi.Env):
                                      sol.J_ref_layout(fi), vis.N,
                                      vis.Tdelta, Hadd)
         sI = 0.5 * (vals[:, 0] + vals[:, 3])
-        img = rimg.dirty_image(vis.uvw, sI, float(vis.freqs[fi]), self.Ninf)
+        image = rimg.dft_image if self.imager == "dft" else rimg.dirty_image
+        img = image(vis.uvw, sI, float(vis.freqs[fi]), self.Ninf)
         return img.unsqueeze(0).cpu().numpy().astype(np.float32)
 
     def calculate_reward_(self, Kselected: int) -> float:

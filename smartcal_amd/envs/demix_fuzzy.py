@@ -23,12 +23,13 @@ class FuzzyDemixingEnv(DemixingEnv):
                  Npix: int = 1024, Tdelta: int = 10, provide_hint=False,
                  provide_influence=False, N_stations: int = 26,
                  Ts: int = 2, poly_order: int = 2, device=None,
-                 seed: int | None = None):
+                 seed: int | None = None, imager: str = "grid"):
         super().__init__(K=K, Nf=Nf, Ninf=Ninf, Npix=Npix, Tdelta=Tdelta,
                          provide_hint=provide_hint,
                          provide_influence=provide_influence,
                          N_stations=N_stations, Ts=Ts,
-                         poly_order=poly_order, device=device, seed=seed)
+                         poly_order=poly_order, device=device, seed=seed,
+                         imager=imager)
         self.n_fuzzy = 32
         self.n_action = 24 * (K - 1) + 8
         self.n_metadata = 5 * K + 2

@@ -5,6 +5,7 @@
 #include <c10/hip/HIPStream.h>
 #include <torch/extension.h>
 
+#include <algorithm>
 #include <tuple>
 
 #include "common.h"
@@ -93,6 +94,12 @@ extern "C" __global__ void station_beam_kernel(const double*, const double*,
 extern "C" __global__ void coherency_beam_kernel(
     const double*, const double*, const int*, const double*, const int*,
     const int*, float*, double, int, int, int, int, int, int);
+extern "C" __global__ void dft_image_kernel(const double*, const float2*,
+                                            const double*, float*, double*,
+                                            double, double, long, int, int,
+                                            int, int);
+extern "C" __global__ void dft_image_reduce_kernel(const double*, float*,
+                                                   long, int);
 struct c32h2 { float x, y; };
 extern "C" __global__ void hessianres_kernel(
     const c32h2*, const c32h2*, const c32h2*, const int*, const int*,
@@ -988,6 +995,67 @@ at::Tensor coherency_beam_predict(const at::Tensor& uvw_scaled,
   return C;
 }
 
+// Direct-Fourier-sum image cube (dft_image.hip) in one launch: uvw (S, 3)
+// f64 metres, vals (F, M, S) complex64 with weights and normalisation
+// folded in, fpar (F, 2) f64 rows [f/c, cell]; image centre (lc, mc).
+// Returns (F, M, npix, npix) f32. nsplit slices the sample range over
+// blockIdx.z (0 = choose for occupancy); more than one slice adds a
+// fixed-order reduction launch.
+at::Tensor dft_image(const at::Tensor& uvw, const at::Tensor& vals,
+                     const at::Tensor& fpar, int64_t npix, double lc,
+                     double mc, int64_t nsplit) {
+  TORCH_CHECK(uvw.is_cuda() && uvw.scalar_type() == at::kDouble
+              && uvw.is_contiguous() && uvw.dim() == 2 && uvw.size(1) == 3,
+              "uvw must be f64 contiguous (S, 3) on the GPU");
+  TORCH_CHECK(vals.is_cuda() && vals.scalar_type() == at::kComplexFloat
+              && vals.is_contiguous() && vals.dim() == 3,
+              "vals must be contiguous complex64 (F, M, S) on the GPU");
+  TORCH_CHECK(fpar.is_cuda() && fpar.scalar_type() == at::kDouble
+              && fpar.is_contiguous() && fpar.dim() == 2
+              && fpar.size(1) == 2, "fpar must be f64 contiguous (F, 2)");
+  const int64_t S = uvw.size(0), F = vals.size(0), M = vals.size(1);
+  TORCH_CHECK(vals.size(2) == S, "vals has ", vals.size(2),
+              " samples, uvw has ", S);
+  TORCH_CHECK(fpar.size(0) == F, "fpar rows = ", fpar.size(0), ", F = ", F);
+  TORCH_CHECK(npix >= 1 && npix <= 16384, "npix = ", npix);
+  TORCH_CHECK(F <= 65535 && M <= 65535, "dft_image grid limits: F = ", F,
+              ", M = ", M);
+  TORCH_CHECK(nsplit >= 0 && nsplit <= 65535, "nsplit = ", nsplit);
+  auto out = at::zeros({F, M, npix, npix}, uvw.options().dtype(at::kFloat));
+  if (F == 0 || M == 0 || S == 0) return out;
+  const int64_t nt = (npix + 15) / 16;
+  if (nsplit == 0) {
+    // about 8 blocks per CU, at least one LDS chunk of samples per slice
+    const int64_t want = (2048 + nt * nt * F - 1) / (nt * nt * F);
+    nsplit = std::max<int64_t>(
+        1, std::min<int64_t>({want, S / 256, (int64_t)64}));
+  }
+  at::Tensor part;
+  if (nsplit > 1)
+    part = at::empty({nsplit, F, M, npix, npix},
+                     uvw.options().dtype(at::kDouble));
+  dim3 grid((unsigned)(nt * nt), (unsigned)F, (unsigned)nsplit);
+  hipLaunchKernelGGL(dft_image_kernel, grid, dim3(256), 0, stream(),
+                     uvw.data_ptr<double>(),
+                     reinterpret_cast<const float2*>(vals.data_ptr()),
+                     fpar.data_ptr<double>(), out.data_ptr<float>(),
+                     nsplit > 1 ? part.data_ptr<double>() : nullptr, lc, mc,
+                     (long)S, (int)M, (int)npix, (int)F, (int)nsplit);
+  hipError_t err = hipGetLastError();
+  TORCH_CHECK(err == hipSuccess, "dft_image_kernel launch: ",
+              hipGetErrorString(err));
+  if (nsplit > 1) {
+    const long n = out.numel();
+    hipLaunchKernelGGL(dft_image_reduce_kernel, dim3((n + 255) / 256),
+                       dim3(256), 0, stream(), part.data_ptr<double>(),
+                       out.data_ptr<float>(), n, (int)nsplit);
+    err = hipGetLastError();
+    TORCH_CHECK(err == hipSuccess, "dft_image_reduce_kernel launch: ",
+                hipGetErrorString(err));
+  }
+  return out;
+}
+
 // Shapelet sources of all clusters, added into C in one launch.
 // hdr (Ns,12) f64, coff (Ns) i32 offsets into the packed coef (f64),
 // clk (Kc) i32 cluster index per grid row, soff (Kc+1) i32 source ranges.
@@ -1139,6 +1207,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("q") = py::none(), py::arg("sbase") = 0);
   m.def("station_beam", &station_beam);
   m.def("coherency_beam_predict", &coherency_beam_predict);
+  m.def("dft_image", &dft_image, py::arg("uvw"), py::arg("vals"),
+        py::arg("fpar"), py::arg("npix"), py::arg("lc"), py::arg("mc"),
+        py::arg("nsplit") = 0);
   m.def("hessianres", &hessianres);
   m.def("two_loop_apply", &two_loop_apply);
   m.def("gather_sum", &gather_sum);
