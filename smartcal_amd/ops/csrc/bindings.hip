@@ -79,7 +79,7 @@ extern "C" __global__ void cgemm_nn_bcast_kernel(const float*, const float*,
                                                  int);
 extern "C" __global__ void coherency_kernel(const double*, const double*,
                                             const int*, float*, double,
-                                            int, int);
+                                            int, int, int);
 extern "C" __global__ void shapelet_kernel(const double*, const double*,
                                            const int*, const double*,
                                            const int*, const int*, float*,
@@ -876,26 +876,46 @@ at::Tensor hessianres(const at::Tensor& C, const at::Tensor& R,
   return H;
 }
 
+namespace {
+
+// Shared checks of the coherency bindings: uvw (T, 3) f64, the source
+// table (S, 11) f64 and the cluster offsets (K+1) int32, all on the GPU.
+void check_sky_tables(const at::Tensor& uvw_scaled, const at::Tensor& src,
+                      const at::Tensor& off) {
+  TORCH_CHECK(uvw_scaled.is_cuda()
+              && uvw_scaled.scalar_type() == at::kDouble
+              && uvw_scaled.is_contiguous() && uvw_scaled.dim() == 2
+              && uvw_scaled.size(1) == 3, "uvw must be f64 contiguous (T, 3)");
+  TORCH_CHECK(src.is_cuda() && src.scalar_type() == at::kDouble
+              && src.is_contiguous() && src.dim() == 2 && src.size(1) == 11,
+              "src table must be f64 contiguous (S, 11)");
+  TORCH_CHECK(off.is_cuda() && off.scalar_type() == at::kInt
+              && off.is_contiguous() && off.numel() >= 1,
+              "offsets must be int32");
+}
+
+}  // namespace
+
 // Whole-sky coherency prediction in one launch (N8).
 at::Tensor coherency_predict(const at::Tensor& uvw_scaled,
                              const at::Tensor& src, const at::Tensor& off,
                              double fdelta) {
-  TORCH_CHECK(uvw_scaled.is_cuda()
-              && uvw_scaled.scalar_type() == at::kDouble
-              && uvw_scaled.is_contiguous(), "uvw must be f64 contiguous");
-  TORCH_CHECK(src.scalar_type() == at::kDouble && src.is_contiguous(),
-              "src table must be f64 contiguous");
-  TORCH_CHECK(off.scalar_type() == at::kInt, "offsets must be int32");
+  check_sky_tables(uvw_scaled, src, off);
   const int T = uvw_scaled.size(0);
   const int K = off.numel() - 1;
-  TORCH_CHECK(src.size(1) == 11, "src table must be (S, 11)");
+  TORCH_CHECK(K <= 65535, "coherency grid limit: K = ", K);
   auto C = at::zeros({K, T, 4},
                      uvw_scaled.options().dtype(at::kComplexFloat));
+  if (K == 0 || T == 0) return C;
   dim3 grid((T + 255) / 256, K);
   hipLaunchKernelGGL(coherency_kernel, grid, dim3(256), 0, stream(),
                      uvw_scaled.data_ptr<double>(), src.data_ptr<double>(),
                      off.data_ptr<int>(),
-                     reinterpret_cast<float*>(C.data_ptr()), fdelta, T, K);
+                     reinterpret_cast<float*>(C.data_ptr()), fdelta, T,
+                     (int)src.size(0), K);
+  const hipError_t err = hipGetLastError();
+  TORCH_CHECK(err == hipSuccess, "coherency_kernel launch: ",
+              hipGetErrorString(err));
   return C;
 }
 
@@ -952,23 +972,14 @@ void check_beam_tables(const at::Tensor& E, const at::Tensor& p,
 
 }  // namespace
 
-// Beam-weighted whole-sky coherency prediction in one launch (beam.hip);
+// Beam-weighted whole-sky coherency prediction in one launch;
 // rows of src index the source axis of E.
 at::Tensor coherency_beam_predict(const at::Tensor& uvw_scaled,
                                   const at::Tensor& src,
                                   const at::Tensor& off, double fdelta,
                                   const at::Tensor& E, const at::Tensor& p,
                                   const at::Tensor& q) {
-  TORCH_CHECK(uvw_scaled.is_cuda()
-              && uvw_scaled.scalar_type() == at::kDouble
-              && uvw_scaled.is_contiguous() && uvw_scaled.dim() == 2
-              && uvw_scaled.size(1) == 3, "uvw must be f64 contiguous (T, 3)");
-  TORCH_CHECK(src.is_cuda() && src.scalar_type() == at::kDouble
-              && src.is_contiguous() && src.dim() == 2 && src.size(1) == 11,
-              "src table must be f64 contiguous (S, 11)");
-  TORCH_CHECK(off.is_cuda() && off.scalar_type() == at::kInt
-              && off.is_contiguous() && off.numel() >= 1,
-              "offsets must be int32");
+  check_sky_tables(uvw_scaled, src, off);
   const int64_t T = uvw_scaled.size(0);
   check_beam_tables(E, p, q, T);
   TORCH_CHECK(src.size(0) <= E.size(1), "E covers ", E.size(1),

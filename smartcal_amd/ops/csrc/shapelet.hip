@@ -29,25 +29,16 @@
 // Per-source header row (12 doubles, precomputed host-side):
 //   [l0, m0, n0c, sI_f, sQ_f, sU_f, βa, βb, cosθ, sinθ, 2πβab, n0]
 
-#include "common.h"
+#include "sky_term.h"
 
 #define SHP_THREADS 128
 #define SHP_MAXN 32      // n0 cap: 32² doubles of coefficients = 8 KB
 #define SHP_HDR 12
 #define PI_M14 0.75112554446494248      // π^(−1/4)
 
-// Station-beam gain table of shapelet_beam_kernel (see beam.hip): source s
-// of timeslot t/B on baseline b = t%B = (P[b], Q[b]) is weighted by
-// E[t/B, sbase+s, p] · conj(E[t/B, sbase+s, q]), taken at the source centre.
-struct ShpGain {
-  const double* E;     // (Tt, Sall, N) interleaved complex128
-  const int* P;        // (B)
-  const int* Q;        // (B)
-  int B, N, Sall, sbase;
-};
-
 // BEAM = false is shapelet_kernel as it has always been: `gain` is unused
-// and every beam statement is compiled out.
+// and every beam statement is compiled out. BEAM = true weights source s of
+// sample t = ts·B + b by the station-beam gain (sky_term.h) at its centre.
 template <bool BEAM>
 __device__ __forceinline__ void shapelet_body(
     const double* __restrict__ UVW,   // (T, 3) pre-scaled by 2πf/c
@@ -57,7 +48,7 @@ __device__ __forceinline__ void shapelet_body(
     const int* __restrict__ CLK,      // (Kc) cluster index k in C
     const int* __restrict__ SOFF,     // (Kc+1) source ranges per cluster
     float* __restrict__ C,            // (K, T, 4) interleaved complex64
-    double fdelta, int T, int K, int Ns, long ncoef, const ShpGain& gain) {
+    double fdelta, int T, int K, int Ns, long ncoef, const BeamGain& gain) {
   __shared__ double cs[SHP_MAXN * SHP_MAXN];          // 8 KB
   __shared__ double pv[SHP_MAXN * SHP_THREADS];       // 32 KB, [j][thread]
   __shared__ double r1[SHP_MAXN], r2[SHP_MAXN];
@@ -88,11 +79,8 @@ __device__ __forceinline__ void shapelet_body(
   const double* eq = nullptr;
   if constexpr (BEAM) {
     if (t < T) {
-      const int ts = t / gain.B, b = t - ts * gain.B;
-      const double* et = &gain.E[((long)ts * gain.Sall + gain.sbase)
-                                 * gain.N * 2];
-      ep = &et[2 * min(max(gain.P[b], 0), gain.N - 1)];
-      eq = &et[2 * min(max(gain.Q[b], 0), gain.N - 1)];
+      const int ts = t / gain.B;
+      beam_rows(gain, ts, t - ts * gain.B, ep, eq);
     }
   }
 
@@ -151,19 +139,13 @@ __device__ __forceinline__ void shapelet_body(
       }
       const double ph = u * h[0] + v * h[1] + w * h[2];
       double amp = h[10];
-      if (fdelta > 0.0) {
-        const double x = ph * (0.5 * fdelta);
-        amp *= (fabs(x) < 1e-12) ? 1.0 : fabs(sin(x) / x);
-      }
+      if (fdelta > 0.0) amp *= sky_smear(ph, fdelta);
       const double cp = amp * cos(ph), sp = amp * sin(ph);
       double g_re = cp * f_re - sp * f_im;
       double g_im = cp * f_im + sp * f_re;
       if constexpr (BEAM) {
-        const long o = (long)s * gain.N * 2;
-        const double pr = ep[o], pi = ep[o + 1];
-        const double qr = eq[o], qi = eq[o + 1];
-        const double b_re = pr * qr + pi * qi;       // E_p · conj(E_q)
-        const double b_im = pi * qr - pr * qi;
+        double b_re, b_im;
+        beam_gain(ep, eq, (long)s * gain.N * 2, b_re, b_im);
         const double t_re = b_re * g_re - b_im * g_im;
         g_im = b_re * g_im + b_im * g_re;
         g_re = t_re;
@@ -195,7 +177,7 @@ extern "C" __global__ __launch_bounds__(SHP_THREADS) void shapelet_kernel(
     float* __restrict__ C, double fdelta, int T, int K, int Ns,
     long ncoef) {
   shapelet_body<false>(UVW, HDR, COFF, COEF, CLK, SOFF, C, fdelta, T, K, Ns,
-                       ncoef, ShpGain{});
+                       ncoef, BeamGain{});
 }
 
 extern "C" __global__ __launch_bounds__(SHP_THREADS) void shapelet_beam_kernel(
@@ -206,5 +188,5 @@ extern "C" __global__ __launch_bounds__(SHP_THREADS) void shapelet_beam_kernel(
     const double* __restrict__ E, const int* __restrict__ P,
     const int* __restrict__ Q, int B, int N, int Sall, int sbase) {
   shapelet_body<true>(UVW, HDR, COFF, COEF, CLK, SOFF, C, fdelta, T, K, Ns,
-                      ncoef, ShpGain{E, P, Q, B, N, Sall, sbase});
+                      ncoef, BeamGain{E, P, Q, B, N, Sall, sbase});
 }

@@ -171,7 +171,7 @@ def _add_shapelets_torch(C, u, v, w, tables, fdelta, beam=None, freq=None):
             F = (pu * (cij @ pv.to(torch.complex128))).sum(dim=0)
             ph = u * l0 + v * m0 + w * n0c
             amp = torch.full_like(ph, norm)
-            if fdelta is not None:
+            if fdelta:
                 amp = amp * torch.abs(torch.sinc(ph * (0.5 * fdelta / math.pi)))
             G = torch.polar(amp, ph) * F
             if beam is not None:
@@ -217,7 +217,7 @@ def predict_coherencies_uvw(sky: SkyModel, clusters: ClusterSet,
     u = uvw[:, 0].double() * scale
     v = uvw[:, 1].double() * scale
     w = uvw[:, 2].double() * scale
-    fdelta = (smear_bw / freq) if smear_bw is not None else None
+    fdelta = (smear_bw / freq) if smear_bw is not None else 0.0   # 0 = off
     shp = _shapelet_tables(sky, clusters, ra0, dec0, freq)
 
     from ..ops import use_hip
@@ -226,121 +226,108 @@ def predict_coherencies_uvw(sky: SkyModel, clusters: ClusterSet,
         # one more for all shapelet sources (ops/csrc/shapelet.hip);
         # the torch composition below is the CPU oracle
         uvw_scaled = torch.stack((u, v, w), dim=1).contiguous()
-        if beam is not None:
-            return _predict_hip_beam(sky, clusters, uvw_scaled, freq, ra0,
-                                     dec0, fdelta if fdelta is not None
-                                     else 0.0, shp, beam)
-        C = _predict_hip(sky, clusters, uvw_scaled, freq, ra0, dec0,
-                         fdelta if fdelta is not None else 0.0)
-        if shp is not None:
-            from ..ops import ext
-            ext().shapelet_predict(
-                C, uvw_scaled, *(torch.as_tensor(a, device=device)
-                                 for a in shp),
-                fdelta if fdelta is not None else 0.0)
-        return C
+        return _predict_hip(sky, clusters, uvw_scaled, freq, ra0, dec0,
+                            fdelta, shp, beam)
 
     K = len(clusters)
     C = torch.zeros((K, T, 4), dtype=torch.complex64, device=device)
     if beam is not None:
         p_idx, q_idx = baseline_pq(beam.n_stations, device)
-    for ck, cluster in enumerate(clusters):
-        lmn, flux, eX2, eY2, eP, gflag = _cluster_source_tensors(
-            sky, cluster, ra0, dec0, freq, device)
-        S = lmn.shape[0]
+    src, off = _source_table(sky, clusters, device, freq, ra0, dec0)
+    off = off.tolist()
+    u1, v1, w1 = u.unsqueeze(1), v.unsqueeze(1), w.unsqueeze(1)
+    for ck in range(K):
+        rows = src[off[ck]:off[ck + 1]]
         acc = torch.zeros(T, dtype=torch.complex128, device=device)
         if beam is not None:
-            E = array_factor(beam, lmn, freq)                    # (Tt,N,S)
-        for s0 in range(0, S, chunk):
-            s1 = min(s0 + chunk, S)
-            lm = lmn[s0:s1]                                      # (s,3)
+            E = array_factor(beam, rows[:, 0:3].contiguous(), freq)  # (Tt,N,S)
+        for s0 in range(0, rows.shape[0], chunk):
+            r = rows[s0:s0 + chunk]
             # (T,s) phase — GEMM shape
-            ph = u.unsqueeze(1) * lm[:, 0] + v.unsqueeze(1) * lm[:, 1] \
-                + w.unsqueeze(1) * lm[:, 2]
-            amp = flux[s0:s1].expand(T, s1 - s0).clone()
-            if fdelta is not None:
+            ph = u1 * r[:, 0] + v1 * r[:, 1] + w1 * r[:, 2]
+            amp = r[:, 3].expand(T, r.shape[0]).clone()
+            if fdelta:
                 amp = amp * torch.abs(torch.sinc(ph * (0.5 * fdelta / math.pi)))
-            g = gflag[s0:s1]
-            if bool(g.any()):
-                gi = torch.nonzero(g, as_tuple=True)[0]
-                ll, mm, nn = lm[gi, 0], lm[gi, 1], lm[gi, 2]
-                # projection of uv onto the source tangent plane
-                # (`calibration_tools.py:425-441`)
-                # note: nn is (n-1) as returned by radectolm; the reference
-                # takes acos of that value directly (`calibration_tools.py:425`)
-                phi = -torch.acos(torch.clamp(nn, -1.0, 1.0))
-                xi = -torch.atan2(-ll, mm)
-                cxi, sxi = torch.cos(xi), torch.sin(xi)
-                cphi, sphi = torch.cos(phi), torch.sin(phi)
-                uup = u.unsqueeze(1) * cxi - v.unsqueeze(1) * cphi * sxi \
-                    + w.unsqueeze(1) * sphi * sxi
-                vvp = u.unsqueeze(1) * sxi + v.unsqueeze(1) * cphi * cxi \
-                    - w.unsqueeze(1) * sphi * cxi
-                cpa, spa = torch.cos(eP[gi]), torch.sin(eP[gi])
-                uut = 2.0 * eX2[gi] * (cpa * uup - spa * vvp)
-                vvt = 2.0 * eY2[gi] * (spa * uup + cpa * vvp)
+            gi = torch.nonzero(r[:, 4], as_tuple=True)[0]
+            if gi.numel():
+                # Gaussian envelope from the six coefficients of the row
+                uut = u1 * r[gi, 5] + v1 * r[gi, 6] + w1 * r[gi, 7]
+                vvt = u1 * r[gi, 8] + v1 * r[gi, 9] + w1 * r[gi, 10]
                 amp[:, gi] = amp[:, gi] * (0.5 * math.pi
                                            * torch.exp(-(uut * uut + vvt * vvt)))
+            term = torch.polar(amp, ph)
             if beam is not None:
-                acc = acc + (torch.polar(amp, ph)
-                             * _beam_gain(E[:, :, s0:s1], p_idx,
-                                          q_idx)).sum(dim=1)
-                continue
-            acc = acc + (torch.polar(amp, ph)).sum(dim=1)
+                term = term * _beam_gain(E[:, :, s0:s0 + chunk], p_idx, q_idx)
+            acc = acc + term.sum(dim=1)
         C[ck, :, 0] = acc.to(torch.complex64)
         C[ck, :, 3] = C[ck, :, 0]
     if shp is not None:
-        if beam is not None:
-            _add_shapelets_torch(C, u, v, w, shp, fdelta, beam, freq)
-        else:
-            _add_shapelets_torch(C, u, v, w, shp, fdelta)
+        _add_shapelets_torch(C, u, v, w, shp, fdelta, beam, freq)
     return C
 
 
-def _predict_hip(sky, clusters, uvw_scaled, freq, ra0, dec0, fdelta):
-    """Build the per-source coefficient table and run the HIP kernel.
-
-    Table row: [l, m, n, flux, gflag, gu1, gv1, gw1, gu2, gv2, gw2] —
-    the Gaussian projected-envelope rotation is linear in (u, v, w), so
-    it collapses to 6 per-source coefficients (see coherency.hip)."""
-    from ..ops import ext
-
-    src, off = _source_table(sky, clusters, uvw_scaled.device, freq, ra0,
-                             dec0)
-    return ext().coherency_predict(uvw_scaled, src, off, float(fdelta))
-
-
-def _predict_hip_beam(sky, clusters, uvw_scaled, freq, ra0, dec0, fdelta,
-                      shp, beam):
-    """Beam-weighted prediction on the kernels of ops/csrc/beam.hip: one
-    launch builds E for all point/Gaussian rows and all shapelet centres,
-    one predicts the point/Gaussian coherencies, one adds the shapelets."""
+def _predict_hip(sky, clusters, uvw_scaled, freq, ra0, dec0, fdelta,
+                 shp=None, beam=None):
+    """Build the per-source table and run the HIP kernels: one launch
+    predicts the point/Gaussian coherencies, one more adds the shapelet
+    sources of ``shp`` (`_shapelet_tables`). With ``beam``, one launch
+    first builds E for all point/Gaussian rows and all shapelet centres
+    (ops/csrc/beam.hip) and both predictions are weighted by it."""
     from ..ops import ext
 
     device = uvw_scaled.device
     src, off = _source_table(sky, clusters, device, freq, ra0, dec0)
-    lmn = src[:, 0:3]
-    if shp is not None:
-        lmn = torch.cat((lmn, torch.as_tensor(
-            np.ascontiguousarray(shp[0][:, 0:3]), device=device)))
-    elem = torch.as_tensor(beam.elem_uvw, dtype=torch.float64,
-                           device=device).contiguous()
-    E = ext().station_beam(elem, lmn.contiguous(),
-                           2.0 * math.pi / C_LIGHT * freq)
-    p_idx, q_idx = (i.to(torch.int32)
-                    for i in baseline_pq(beam.n_stations, device))
-    C = ext().coherency_beam_predict(uvw_scaled, src, off, float(fdelta), E,
-                                     p_idx, q_idx)
+    gain = ()
+    if beam is not None:
+        lmn = src[:, 0:3]
+        if shp is not None:
+            lmn = torch.cat((lmn, torch.as_tensor(
+                np.ascontiguousarray(shp[0][:, 0:3]), device=device)))
+        elem = torch.as_tensor(beam.elem_uvw, dtype=torch.float64,
+                               device=device).contiguous()
+        E = ext().station_beam(elem, lmn.contiguous(),
+                               2.0 * math.pi / C_LIGHT * freq)
+        p_idx, q_idx = (i.to(torch.int32)
+                        for i in baseline_pq(beam.n_stations, device))
+        # shapelet centres follow the src.shape[0] rows of the table in E
+        gain = (E, p_idx, q_idx, src.shape[0])
+        C = ext().coherency_beam_predict(uvw_scaled, src, off, float(fdelta),
+                                         *gain[:3])
+    else:
+        C = ext().coherency_predict(uvw_scaled, src, off, float(fdelta))
     if shp is not None:
         ext().shapelet_predict(
             C, uvw_scaled, *(torch.as_tensor(a, device=device) for a in shp),
-            float(fdelta), E, p_idx, q_idx, src.shape[0])
+            float(fdelta), *gain)
     return C
 
 
+def _gaussian_coeffs(lmn, eX2, eY2, eP):
+    """Projected envelope of Gaussian sources (`calibration_tools.py:
+    424-448`) → (gu (S, 3), gv (S, 3)). The projection of uv onto the
+    source tangent plane and the position-angle rotation are linear in
+    (u, v, w), so ``uut = gu·(u, v, w)``, ``vvt = gv·(u, v, w)`` and the
+    envelope is π/2 · exp(−(uut² + vvt²)). Note: lmn[:, 2] is (n − 1) as
+    returned by radectolm; the reference takes acos of that value directly
+    (`calibration_tools.py:425`)."""
+    ll, mm, nn = lmn[:, 0], lmn[:, 1], lmn[:, 2]
+    phi = -torch.acos(torch.clamp(nn, -1.0, 1.0))
+    xi = -torch.atan2(-ll, mm)
+    cxi, sxi = torch.cos(xi), torch.sin(xi)
+    cphi, sphi = torch.cos(phi), torch.sin(phi)
+    cpa, spa = torch.cos(eP), torch.sin(eP)
+    # uup = (cxi)u + (-cphi sxi)v + (sphi sxi)w; vvp likewise
+    up = torch.stack((cxi, -cphi * sxi, sphi * sxi), dim=1)
+    vp = torch.stack((sxi, cphi * cxi, -sphi * cxi), dim=1)
+    return (2.0 * eX2[:, None] * (cpa[:, None] * up - spa[:, None] * vp),
+            2.0 * eY2[:, None] * (spa[:, None] * up + cpa[:, None] * vp))
+
+
 def _source_table(sky, clusters, device, freq, ra0, dec0):
-    """→ (src (Stot, 11) f64, off (K+1,) i32): the rows of `_predict_hip`
-    for all clusters and the clusters' offsets into them."""
+    """→ (src (Stot, 11) f64, off (K+1,) i32): the rows
+    [l, m, n, flux, gflag, gu1, gv1, gw1, gu2, gv2, gw2] of both
+    prediction paths (see ops/csrc/sky_term.h) for all clusters, and the
+    clusters' offsets into them."""
     rows = []
     offs = [0]
     for cluster in clusters:
@@ -353,23 +340,13 @@ def _source_table(sky, clusters, device, freq, ra0, dec0):
         g = gflag.to(torch.bool)
         if bool(g.any()):
             gi = torch.nonzero(g, as_tuple=True)[0]
-            ll, mm, nn = lmn[gi, 0], lmn[gi, 1], lmn[gi, 2]
-            phi = -torch.acos(torch.clamp(nn, -1.0, 1.0))
-            xi = -torch.atan2(-ll, mm)
-            cxi, sxi = torch.cos(xi), torch.sin(xi)
-            cphi, sphi = torch.cos(phi), torch.sin(phi)
-            cpa, spa = torch.cos(eP[gi]), torch.sin(eP[gi])
-            # uup = (cxi)u + (-cphi sxi)v + (sphi sxi)w; vvp likewise
-            up = torch.stack((cxi, -cphi * sxi, sphi * sxi), dim=1)
-            vp = torch.stack((sxi, cphi * cxi, -sphi * cxi), dim=1)
             tab[gi, 4] = 1.0
-            tab[gi, 5:8] = 2.0 * eX2[gi, None] * (cpa[:, None] * up
-                                                  - spa[:, None] * vp)
-            tab[gi, 8:11] = 2.0 * eY2[gi, None] * (spa[:, None] * up
-                                                   + cpa[:, None] * vp)
+            tab[gi, 5:8], tab[gi, 8:11] = _gaussian_coeffs(
+                lmn[gi], eX2[gi], eY2[gi], eP[gi])
         rows.append(tab)
         offs.append(offs[-1] + S)
-    src = torch.cat(rows).contiguous()
+    src = torch.cat(rows).contiguous() if rows else torch.zeros(
+        0, 11, dtype=torch.float64, device=device)
     off = torch.tensor(offs, dtype=torch.int32, device=device)
     return src, off
 
