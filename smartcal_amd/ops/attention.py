@@ -47,8 +47,10 @@ class _AttnFn(torch.autograd.Function):
         # da (grad wrt the returned attention map) is unused by every
         # in-repo consumer (the map is returned for inspection only);
         # supporting it would mean a second softmax-backward path.
-        assert da is None, \
-            "backprop through the returned attention map is unsupported"
+        if da is not None:
+            raise RuntimeError(
+                "scaled_dot_product: backprop through the returned "
+                "attention map is unsupported on the HIP path")
         a, q, k, v = ctx.saved_tensors
         if do is None:
             return None, None, None
@@ -60,14 +62,21 @@ def scaled_dot_product(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor):
     """Drop-in for the reference's ``scaled_dot_product`` (values, attn).
 
     Accepts (..., T, dh); the HIP path flattens leading dims to one
-    group axis. Falls back to torch off-GPU or beyond the T/dh caps.
+    group axis. Falls back to torch off-GPU, beyond the T/dh caps, and
+    when k or v differ from q in shape or dtype (cross-attention with its
+    own key length, broadcast leading dims): the kernel has one (T, dh).
     """
     T, dh = q.shape[-2], q.shape[-1]
-    if use_hip(q) and T <= _TMAX and dh <= _DMAX and q.dtype == torch.float32:
+    same = (k.shape == q.shape and v.shape == q.shape
+            and k.dtype == q.dtype and v.dtype == q.dtype
+            and k.device == q.device and v.device == q.device)
+    if (use_hip(q) and same and q.dim() >= 2 and T <= _TMAX and 1 <= dh <= _DMAX
+            and q.dtype == torch.float32):
         lead = q.shape[:-2]
-        qf = q.contiguous().reshape(-1, T, dh)
-        kf = k.contiguous().reshape(-1, T, dh)
-        vf = v.contiguous().reshape(-1, T, dh)
+        G = math.prod(lead)  # explicit: -1 is ambiguous for empty inputs
+        qf = q.contiguous().reshape(G, T, dh)
+        kf = k.contiguous().reshape(G, T, dh)
+        vf = v.contiguous().reshape(G, T, dh)
         o, a = _AttnFn.apply(qf, kf, vf)
         return o.reshape(*lead, T, dh), a.reshape(*lead, T, T)
     return _torch_sdp(q, k, v)

@@ -6,6 +6,7 @@
 #include <torch/extension.h>
 
 #include <algorithm>
+#include <climits>
 #include <tuple>
 
 #include "common.h"
@@ -125,6 +126,14 @@ inline void check_f32(const at::Tensor& t, const char* name) {
 
 inline hipStream_t stream() {
   return c10::hip::getCurrentHIPStream().stream();
+}
+
+// Read the status of the launch just issued, so that a refused launch
+// raises here and does not leave its error for the next binding.
+inline void check_launch(const char* kernel) {
+  const hipError_t err = hipGetLastError();
+  TORCH_CHECK(err == hipSuccess, kernel, " launch: ",
+              hipGetErrorString(err));
 }
 
 std::tuple<at::Tensor, at::Tensor, at::Tensor> fused_linear_fwd(
@@ -425,18 +434,30 @@ at::Tensor conv2d_k5s2_fwd(const at::Tensor& x, const at::Tensor& W,
                            const c10::optional<at::Tensor>& bias) {
   check_f32(x, "x");
   check_f32(W, "W");
+  TORCH_CHECK(x.dim() == 4 && W.dim() == 4,
+              "conv2d_k5s2: x must be (B, Cin, H, W), weight 4-D");
   const int B = x.size(0), Cin = x.size(1), H = x.size(2), Wd = x.size(3);
   const int Cout = W.size(0);
   TORCH_CHECK(W.size(1) == Cin && W.size(2) == 5 && W.size(3) == 5,
               "conv2d_k5s2: weight must be (Cout, Cin, 5, 5)");
+  // below 5 the C division would still give one window, outside the image
+  TORCH_CHECK(H >= 5 && Wd >= 5, "conv2d_k5s2: the image (", H, " x ", Wd,
+              ") is smaller than the 5 x 5 kernel");
+  if (bias) {
+    check_f32(*bias, "bias");
+    TORCH_CHECK(bias->numel() == Cout, "conv2d_k5s2: bias must hold Cout");
+  }
   const int OH = (H - 5) / 2 + 1, OW = (Wd - 5) / 2 + 1;
   auto y = at::empty({B, Cout, OH, OW}, x.options());
   const long total = (long)B * Cout * OH * OW;
+  if (total == 0) return y;
+  TORCH_CHECK(Cin >= 1, "conv2d_k5s2: no input channels");
   hipLaunchKernelGGL(conv2d_k5s2_fwd_kernel,
                      dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
                      stream(), x.data_ptr<float>(), W.data_ptr<float>(),
                      bias ? bias->data_ptr<float>() : nullptr,
                      y.data_ptr<float>(), B, Cin, H, Wd, Cout, OH, OW);
+  check_launch("conv2d_k5s2_fwd_kernel");
   return y;
 }
 
@@ -445,20 +466,37 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> conv2d_k5s2_bwd(
   check_f32(dy, "dy");
   check_f32(x, "x");
   check_f32(W, "W");
+  TORCH_CHECK(x.dim() == 4 && W.dim() == 4 && dy.dim() == 4,
+              "conv2d_k5s2_bwd: dy, x and weight must be 4-D");
   const int B = x.size(0), Cin = x.size(1), H = x.size(2), Wd = x.size(3);
-  const int Cout = W.size(0), OH = dy.size(2), OW = dy.size(3);
-  auto dx = at::empty_like(x);
-  auto dW = at::empty_like(W);
-  auto db = at::empty({Cout}, x.options());
+  const int Cout = W.size(0);
+  TORCH_CHECK(W.size(1) == Cin && W.size(2) == 5 && W.size(3) == 5,
+              "conv2d_k5s2_bwd: weight must be (Cout, Cin, 5, 5)");
+  TORCH_CHECK(H >= 5 && Wd >= 5, "conv2d_k5s2_bwd: the image (", H, " x ",
+              Wd, ") is smaller than the 5 x 5 kernel");
+  const int OH = (H - 5) / 2 + 1, OW = (Wd - 5) / 2 + 1;
+  TORCH_CHECK(dy.size(0) == B && dy.size(1) == Cout && dy.size(2) == OH
+              && dy.size(3) == OW, "conv2d_k5s2_bwd: dy must be (", B, ", ",
+              Cout, ", ", OH, ", ", OW, "), got ", dy.sizes());
   const long totx = (long)B * Cin * H * Wd;
+  const bool empty = B == 0 || Cout == 0;
+  TORCH_CHECK(empty || Cin >= 1, "conv2d_k5s2_bwd: no input channels");
+  // an empty batch or channel axis leaves every gradient at zero
+  auto dx = empty ? at::zeros_like(x) : at::empty_like(x);
+  auto dW = empty ? at::zeros_like(W) : at::empty_like(W);
+  auto db = empty ? at::zeros({Cout}, x.options())
+                  : at::empty({Cout}, x.options());
+  if (empty) return {dx, dW, db};
   hipLaunchKernelGGL(conv2d_k5s2_dx_kernel,
                      dim3((unsigned)((totx + 255) / 256)), dim3(256), 0,
                      stream(), dy.data_ptr<float>(), W.data_ptr<float>(),
                      dx.data_ptr<float>(), B, Cin, H, Wd, Cout, OH, OW);
+  check_launch("conv2d_k5s2_dx_kernel");
   hipLaunchKernelGGL(conv2d_k5s2_dw_kernel, dim3(Cout * Cin), dim3(256), 0,
                      stream(), dy.data_ptr<float>(), x.data_ptr<float>(),
                      dW.data_ptr<float>(), db.data_ptr<float>(), B, Cin, H,
                      Wd, Cout, OH, OW);
+  check_launch("conv2d_k5s2_dw_kernel");
   return {dx, dW, db};
 }
 
@@ -541,13 +579,16 @@ at::Tensor fused_linear_bwd_dz_into(
 at::Tensor mfma_gemm_nn(const at::Tensor& A, const at::Tensor& B) {
   check_f32(A, "A");
   check_f32(B, "B");
+  TORCH_CHECK(A.dim() == 2 && B.dim() == 2, "gemm_nn takes two matrices");
   const int M = A.size(0), K = A.size(1), N = B.size(1);
   TORCH_CHECK(B.size(0) == K, "gemm_nn shape mismatch");
   auto C = at::empty({M, N}, A.options());
+  if (M == 0 || N == 0) return C;
   dim3 grid((M + 15) / 16, (N + 63) / 64);
   hipLaunchKernelGGL(gemm_f32_nn_kernel, grid, dim3(256), 0, stream(),
                      A.data_ptr<float>(), B.data_ptr<float>(),
                      C.data_ptr<float>(), M, K, N);
+  check_launch("gemm_f32_nn_kernel");
   return C;
 }
 
@@ -555,17 +596,23 @@ std::tuple<at::Tensor, at::Tensor> mfma_gemm_tn_bias(const at::Tensor& dz,
                                                      const at::Tensor& x) {
   check_f32(dz, "dz");
   check_f32(x, "x");
+  TORCH_CHECK(dz.dim() == 2 && x.dim() == 2, "gemm_tn takes two matrices");
   const int Bb = dz.size(0), N = dz.size(1), K = x.size(1);
   TORCH_CHECK(x.size(0) == Bb, "gemm_tn batch mismatch");
   auto dW = at::empty({N, K}, dz.options());
   auto db = at::empty({N}, dz.options());
-  dim3 grid((N + 15) / 16, (K + 63) / 64);
-  hipLaunchKernelGGL(gemm_f32_tn_kernel, grid, dim3(256), 0, stream(),
-                     dz.data_ptr<float>(), x.data_ptr<float>(),
-                     dW.data_ptr<float>(), nullptr, N, Bb, K, 0);
+  if (N == 0) return {dW, db};
+  if (K > 0) {
+    dim3 grid((N + 15) / 16, (K + 63) / 64);
+    hipLaunchKernelGGL(gemm_f32_tn_kernel, grid, dim3(256), 0, stream(),
+                       dz.data_ptr<float>(), x.data_ptr<float>(),
+                       dW.data_ptr<float>(), nullptr, N, Bb, K, 0);
+    check_launch("gemm_f32_tn_kernel");
+  }
   hipLaunchKernelGGL(colsum_kernel, dim3((N + 63) / 64), dim3(256), 0,
                      stream(), dz.data_ptr<float>(), db.data_ptr<float>(),
                      Bb, N, 0);
+  check_launch("colsum_kernel");
   return {dW, db};
 }
 
@@ -579,15 +626,18 @@ void mfma_gemm_tn_bias_into(const at::Tensor& dz, const at::Tensor& x,
   check_f32(x, "x");
   check_f32(dW, "dW");
   check_f32(db, "db");
+  TORCH_CHECK(dz.dim() == 2 && x.dim() == 2, "gemm_tn takes two matrices");
   const int Bb = dz.size(0), N = dz.size(1), K = x.size(1);
   TORCH_CHECK(x.size(0) == Bb, "gemm_tn batch mismatch");
   TORCH_CHECK(dW.numel() == (int64_t)N * K && db.numel() == N,
               "grad views must hold N*K and N elements");
+  if (N == 0) return;
   dim3 grid((N + 15) / 16, (K + 63) / 64 + 1);
   hipLaunchKernelGGL(gemm_f32_tn_kernel, grid, dim3(256), 0, stream(),
                      dz.data_ptr<float>(), x.data_ptr<float>(),
                      dW.data_ptr<float>(), db.data_ptr<float>(), N, Bb, K,
                      1);
+  check_launch("gemm_f32_tn_kernel");
 }
 
 // ---- bf16-compute variants (fp32 interfaces, bf16 MFMA inside) ----
@@ -655,15 +705,24 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> tanh_gauss_fwd(
     const at::Tensor& mu, const at::Tensor& logsigma, const at::Tensor& eps,
     double max_action) {
   check_f32(mu, "mu");
+  check_f32(logsigma, "logsigma");
+  check_f32(eps, "eps");
+  TORCH_CHECK(mu.dim() == 2, "tanh_gauss_fwd: mu must be (B, A)");
+  TORCH_CHECK(logsigma.sizes() == mu.sizes() && eps.sizes() == mu.sizes(),
+              "tanh_gauss_fwd: logsigma and eps must have mu's shape");
   const int B = mu.size(0), A = mu.size(1);
   auto action = at::empty_like(mu);
   auto at_ = at::empty_like(mu);
-  auto logp = at::empty({B, 1}, mu.options());
+  // a row without actions sums to log-probability 0
+  auto logp = A == 0 ? at::zeros({B, 1}, mu.options())
+                     : at::empty({B, 1}, mu.options());
+  if (B == 0 || A == 0) return {action, logp, at_};
   hipLaunchKernelGGL(tanh_gauss_fwd_kernel, dim3(B), dim3(64), 0, stream(),
                      mu.data_ptr<float>(), logsigma.data_ptr<float>(),
                      eps.data_ptr<float>(), action.data_ptr<float>(),
                      logp.data_ptr<float>(), at_.data_ptr<float>(),
                      (float)max_action, B, A);
+  check_launch("tanh_gauss_fwd_kernel");
   return {action, logp, at_};
 }
 
@@ -672,16 +731,27 @@ std::tuple<at::Tensor, at::Tensor> tanh_gauss_bwd(
     const at::Tensor& logsigma, const at::Tensor& eps, const at::Tensor& at_,
     double max_action) {
   check_f32(dact, "dact");
+  check_f32(dlogp, "dlogp");
+  check_f32(logsigma, "logsigma");
+  check_f32(eps, "eps");
+  check_f32(at_, "at");
+  TORCH_CHECK(dact.dim() == 2, "tanh_gauss_bwd: dact must be (B, A)");
+  TORCH_CHECK(logsigma.sizes() == dact.sizes()
+              && eps.sizes() == dact.sizes() && at_.sizes() == dact.sizes(),
+              "tanh_gauss_bwd: logsigma, eps and at must have dact's shape");
   const int B = dact.size(0), A = dact.size(1);
+  TORCH_CHECK(dlogp.numel() == B, "tanh_gauss_bwd: dlogp must hold B values");
   auto dmu = at::empty_like(dact);
   auto dls = at::empty_like(dact);
   const long n = (long)B * A;
+  if (n == 0) return {dmu, dls};
   hipLaunchKernelGGL(tanh_gauss_bwd_kernel, dim3((n + 255) / 256), dim3(256),
                      0, stream(), dact.data_ptr<float>(),
                      dlogp.data_ptr<float>(), logsigma.data_ptr<float>(),
                      eps.data_ptr<float>(), at_.data_ptr<float>(),
                      dmu.data_ptr<float>(), dls.data_ptr<float>(),
                      (float)max_action, B, A);
+  check_launch("tanh_gauss_bwd_kernel");
   return {dmu, dls};
 }
 
@@ -689,14 +759,24 @@ void fused_adam(at::Tensor& p, const at::Tensor& g, at::Tensor& m,
                 at::Tensor& v, at::Tensor& t_dev, double lr, double b1,
                 double b2, double eps) {
   check_f32(p, "p");
+  check_f32(g, "g");
+  check_f32(m, "m");
+  check_f32(v, "v");
+  check_f32(t_dev, "t_dev");
   const long n = p.numel();
+  TORCH_CHECK(g.numel() == n && m.numel() == n && v.numel() == n,
+              "fused_adam: g, m and v must hold as many values as p");
+  TORCH_CHECK(t_dev.numel() == 1, "fused_adam: t_dev is one step counter");
+  if (n == 0) return;  // no parameters, no step: t_dev stays too
   hipLaunchKernelGGL(fused_adam_kernel, dim3((n + 255) / 256), dim3(256), 0,
                      stream(), p.data_ptr<float>(), g.data_ptr<float>(),
                      m.data_ptr<float>(), v.data_ptr<float>(),
                      t_dev.data_ptr<float>(), (float)lr, (float)b1,
                      (float)b2, (float)eps, n);
+  check_launch("fused_adam_kernel");
   hipLaunchKernelGGL(adam_bump_kernel, dim3(1), dim3(64), 0, stream(),
                      t_dev.data_ptr<float>());
+  check_launch("adam_bump_kernel");
 }
 
 std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> enet_lbfgs_solve(
@@ -759,20 +839,22 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> per_sample(
     const at::Tensor& priorities, const at::Tensor& u, double beta) {
   check_f32(priorities, "priorities");
   check_f32(u, "u");
-  const int n = priorities.numel();
-  const int B = u.numel();
+  const int64_t n = priorities.numel();
+  const int64_t B = u.numel();
   TORCH_CHECK(n >= 1 && n <= PER_LDS_MAX_N,
               "per_sample: n must be in [1, 32768]");
-  TORCH_CHECK(B >= 1 && B <= PER_MAX_B, "per_sample: B must be in [1, 4096]");
+  TORCH_CHECK(B <= PER_MAX_B, "per_sample: B must be in [0, 4096]");
   auto idx = at::empty({B}, priorities.options().dtype(at::kLong));
   auto probs = at::empty({B}, priorities.options());
   auto w = at::empty({B}, priorities.options());
+  if (B == 0) return {idx, probs, w};  // no draws: nothing to launch
   const int T = 256;
   const size_t lds = (size_t)(n + T + 1 + B) * sizeof(float);
   hipLaunchKernelGGL(per_sample_kernel, dim3(1), dim3(T), lds, stream(),
                      priorities.data_ptr<float>(), u.data_ptr<float>(),
                      idx.data_ptr<long>(), probs.data_ptr<float>(),
-                     w.data_ptr<float>(), n, B, (float)beta);
+                     w.data_ptr<float>(), (int)n, (int)B, (float)beta);
+  check_launch("per_sample_kernel");
   return {idx, probs, w};
 }
 
@@ -781,12 +863,19 @@ void per_update(at::Tensor& priorities, const at::Tensor& idx,
                 double max_priority) {
   check_f32(priorities, "priorities");
   check_f32(td, "td");
-  TORCH_CHECK(idx.scalar_type() == at::kLong, "idx must be int64");
-  const int B = idx.numel();
-  hipLaunchKernelGGL(per_update_kernel, dim3((B + 255) / 256), dim3(256), 0,
-                     stream(), priorities.data_ptr<float>(),
-                     idx.data_ptr<long>(), td.data_ptr<float>(), B,
+  TORCH_CHECK(idx.is_cuda() && idx.scalar_type() == at::kLong
+              && idx.is_contiguous(),
+              "idx must be contiguous int64 on the GPU");
+  const int64_t B = idx.numel();
+  TORCH_CHECK(td.numel() == B, "per_update: one td error per index");
+  TORCH_CHECK(B <= INT_MAX, "per_update: too many indices");
+  if (B == 0) return;  // nothing to update
+  TORCH_CHECK(priorities.numel() >= 1, "per_update: empty priority array");
+  hipLaunchKernelGGL(per_update_kernel, dim3((unsigned)((B + 255) / 256)),
+                     dim3(256), 0, stream(), priorities.data_ptr<float>(),
+                     idx.data_ptr<long>(), td.data_ptr<float>(), (int)B,
                      (float)eps, (float)alpha, (float)max_priority);
+  check_launch("per_update_kernel");
 }
 
 // Batched complex64 GEMM with A broadcast over `rep` consecutive batch
@@ -1143,18 +1232,28 @@ std::tuple<at::Tensor, at::Tensor> attn_fwd(const at::Tensor& Q,
   check_f32(Q, "Q");
   check_f32(K, "K");
   check_f32(V, "V");
-  const int G = Q.size(0), T = Q.size(1), dh = Q.size(2);
+  TORCH_CHECK(Q.dim() == 3, "attn_fwd: Q must be (G, T, dh)");
+  // one (T, dh) for all three: the kernel has no separate key length
+  TORCH_CHECK(K.sizes() == Q.sizes() && V.sizes() == Q.sizes(),
+              "attn_fwd: K and V must have Q's shape ", Q.sizes(), ", got ",
+              K.sizes(), " and ", V.sizes(), " (python falls back)");
+  const int64_t G = Q.size(0);
+  const int T = Q.size(1), dh = Q.size(2);
   TORCH_CHECK(T <= 32 && dh <= 96,
               "attn_fwd caps: T <= 32, dh <= 96 (python falls back)");
+  TORCH_CHECK(G <= INT_MAX, "attn_fwd: too many groups");
   auto O = at::empty_like(Q);
   auto A = at::empty({G, T, T}, Q.options());
+  if (G == 0 || T == 0) return {O, A};
+  TORCH_CHECK(dh >= 1, "attn_fwd: dh must be at least 1");
   const int Tp = (T + 15) & ~15;
   const int dp = ((dh + 3) & ~3) + 1;
   const size_t lds = (size_t)(3 * Tp * dp + Tp * (Tp + 1)) * sizeof(float);
-  hipLaunchKernelGGL(attn_fwd_kernel, dim3(G), dim3(64), lds, stream(),
-                     Q.data_ptr<float>(), K.data_ptr<float>(),
+  hipLaunchKernelGGL(attn_fwd_kernel, dim3((unsigned)G), dim3(64), lds,
+                     stream(), Q.data_ptr<float>(), K.data_ptr<float>(),
                      V.data_ptr<float>(), O.data_ptr<float>(),
-                     A.data_ptr<float>(), G, T, dh);
+                     A.data_ptr<float>(), (int)G, T, dh);
+  check_launch("attn_fwd_kernel");
   return {O, A};
 }
 
@@ -1163,19 +1262,35 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> attn_bwd(
     const at::Tensor& K, const at::Tensor& V) {
   check_f32(dO, "dO");
   check_f32(A, "A");
-  const int G = Q.size(0), T = Q.size(1), dh = Q.size(2);
+  check_f32(Q, "Q");
+  check_f32(K, "K");
+  check_f32(V, "V");
+  TORCH_CHECK(Q.dim() == 3, "attn_bwd: Q must be (G, T, dh)");
+  TORCH_CHECK(K.sizes() == Q.sizes() && V.sizes() == Q.sizes()
+              && dO.sizes() == Q.sizes(),
+              "attn_bwd: K, V and dO must have Q's shape ", Q.sizes());
+  const int64_t G = Q.size(0);
+  const int T = Q.size(1), dh = Q.size(2);
+  TORCH_CHECK(A.dim() == 3 && A.size(0) == G && A.size(1) == T
+              && A.size(2) == T, "attn_bwd: A must be (G, T, T)");
+  TORCH_CHECK(T <= 32 && dh <= 96, "attn_bwd caps: T <= 32, dh <= 96");
+  TORCH_CHECK(G <= INT_MAX, "attn_bwd: too many groups");
   auto dQ = at::empty_like(Q);
   auto dK = at::empty_like(Q);
   auto dV = at::empty_like(Q);
+  if (G == 0 || T == 0) return {dQ, dK, dV};
+  TORCH_CHECK(dh >= 1, "attn_bwd: dh must be at least 1");
   const int Tp = (T + 15) & ~15;
   const int dp = ((dh + 3) & ~3) + 1;
   const size_t lds =
       (size_t)(4 * Tp * dp + 2 * Tp * (Tp + 1) + Tp) * sizeof(float);
-  hipLaunchKernelGGL(attn_bwd_kernel, dim3(G), dim3(64), lds, stream(),
-                     dO.data_ptr<float>(), A.data_ptr<float>(),
+  hipLaunchKernelGGL(attn_bwd_kernel, dim3((unsigned)G), dim3(64), lds,
+                     stream(), dO.data_ptr<float>(), A.data_ptr<float>(),
                      Q.data_ptr<float>(), K.data_ptr<float>(),
                      V.data_ptr<float>(), dQ.data_ptr<float>(),
-                     dK.data_ptr<float>(), dV.data_ptr<float>(), G, T, dh);
+                     dK.data_ptr<float>(), dV.data_ptr<float>(), (int)G, T,
+                     dh);
+  check_launch("attn_bwd_kernel");
   return {dQ, dK, dV};
 }
 

@@ -9,8 +9,9 @@
 // prefix sum in LDS (160 KB/CU holds 32k fp32 priorities — every config in
 // the workload family uses mem_size <= 16000), then every thread resolves
 // stratified inverse-CDF targets by binary search on the LDS prefix and
-// computes the importance weight, with the max-weight normalization done by
-// an in-LDS reduction. One launch replaces the torch composition
+// computes the importance weight from the drawn entry's own priority (one
+// global load per draw; the prefix only locates the entry), with the
+// max-weight normalization done by an in-LDS reduction. One launch replaces the torch composition
 // (cumsum + searchsorted + pow + max + div ~ 6 launches) and the reference's
 // O(B log n) host pointer chasing.
 //
@@ -73,8 +74,9 @@ extern "C" __global__ void per_sample_kernel(
       if (pref[mid] < target) loj = mid + 1;
       else hij = mid;
     }
-    const float p = pref[loj] - (loj ? pref[loj - 1] : 0.f);
-    const float prob = p / total;
+    // P(j) from the priority itself: the difference of two fp32 prefix
+    // sums loses the digits the sum has outgrown (third digit at n = 16000)
+    const float prob = PRI[loj] / total;
     IDX[k] = (long)loj;
     PROBS[k] = prob;
     wbuf[k] = powf(fmaxf((float)n * prob, 1e-12f), -beta);

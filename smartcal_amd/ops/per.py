@@ -86,7 +86,9 @@ def update_priorities(priorities: torch.Tensor, idx: torch.Tensor,
     (reference ``enet_sac.py:313-323``)."""
     td = td_errors.detach().reshape(-1).to(torch.float32)
     if use_hip(priorities):
-        ext().per_update(priorities, idx.to(torch.long), td.contiguous(),
+        idx = idx.reshape(-1).to(device=priorities.device, dtype=torch.long)
+        ext().per_update(priorities, idx.contiguous(),
+                         td.to(priorities.device).contiguous(),
                          float(eps), float(alpha), float(max_priority))
         return
     pri = (td.abs() + eps).clamp(max=max_priority).pow(alpha)

@@ -56,16 +56,20 @@ def tanh_gauss_sample(mu: torch.Tensor, logsigma: torch.Tensor,
         logsigma = logsigma.unsqueeze(0)
     if eps is None:
         eps = torch.randn_like(mu)
+    else:
+        # the noise takes mu's dtype and shape, whatever it was drawn as
+        eps = eps.to(mu.dtype).reshape(mu.shape)
     if use_hip(mu):
         mu_c = mu.contiguous()
         logsigma_c = logsigma.contiguous()
+        eps_c = eps.contiguous()
         if reparameterize:
-            action, logprob = _TanhGaussFn.apply(mu_c, logsigma_c, eps,
+            action, logprob = _TanhGaussFn.apply(mu_c, logsigma_c, eps_c,
                                                  float(max_action))
         else:
             with torch.no_grad():
                 action, logprob, _ = ext().tanh_gauss_fwd(
-                    mu_c, logsigma_c, eps, float(max_action))
+                    mu_c, logsigma_c, eps_c, float(max_action))
     else:
         sigma = logsigma.exp()
         if reparameterize:
