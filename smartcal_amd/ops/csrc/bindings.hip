@@ -105,6 +105,8 @@ struct c32h2 { float x, y; };
 extern "C" __global__ void hessianres_kernel(
     const c32h2*, const c32h2*, const c32h2*, const int*, const int*,
     c32h2*, int, int, int, int);
+extern "C" __global__ void hessianres_scale_diag_kernel(c32h2*, int, int,
+                                                        int, int);
 extern "C" __global__ void two_loop_kernel(const float*, const float*,
                                            const float*, float*,
                                            const float*, float, int, long,
@@ -134,6 +136,23 @@ inline void check_launch(const char* kernel) {
   const hipError_t err = hipGetLastError();
   TORCH_CHECK(err == hipSuccess, kernel, " launch: ",
               hipGetErrorString(err));
+}
+
+inline void check_c64(const at::Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_cuda(), name, " must be on the GPU");
+  TORCH_CHECK(t.scalar_type() == at::kComplexFloat, name,
+              " must be complex64");
+  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+}
+
+// An index table the callers build: 1-D, `count` entries of `type`.
+inline void check_index(const at::Tensor& t, at::ScalarType type,
+                        int64_t count, const char* name) {
+  TORCH_CHECK(t.is_cuda(), name, " must be on the GPU");
+  TORCH_CHECK(t.scalar_type() == type, name, " must be ", type);
+  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+  TORCH_CHECK(t.dim() == 1 && t.size(0) == count, name, " must hold ",
+              count, " entries, got ", t.sizes());
 }
 
 std::tuple<at::Tensor, at::Tensor, at::Tensor> fused_linear_fwd(
@@ -506,19 +525,37 @@ std::tuple<at::Tensor, at::Tensor> als_sweep(
     const at::Tensor& C22, const at::Tensor& V22, const at::Tensor& J,
     const at::Tensor& p_idx, const at::Tensor& q_idx,
     const at::Tensor& t_int) {
-  TORCH_CHECK(C22.is_cuda() && C22.scalar_type() == at::kComplexFloat
-              && C22.is_contiguous(), "C22 must be contiguous cfloat GPU");
-  TORCH_CHECK(V22.is_contiguous() && J.is_contiguous(), "contiguous");
-  TORCH_CHECK(p_idx.scalar_type() == at::kInt, "p_idx int32");
-  const int F = C22.size(0), K = C22.size(1), T = C22.size(2),
-            B = C22.size(3);
-  const int Ts = J.size(1), N = J.size(3);
+  check_c64(C22, "C22");
+  check_c64(V22, "V22");
+  check_c64(J, "J");
+  TORCH_CHECK(C22.dim() == 6 && C22.size(4) == 2 && C22.size(5) == 2,
+              "als_sweep: C22 must be (F, K, T, B, 2, 2), got ",
+              C22.sizes());
+  const int64_t F = C22.size(0), K = C22.size(1), T = C22.size(2),
+                B = C22.size(3);
   TORCH_CHECK(K <= 8, "als_sweep supports K <= 8");
+  TORCH_CHECK(V22.dim() == 5 && V22.size(0) == F && V22.size(1) == T
+              && V22.size(2) == B && V22.size(3) == 2 && V22.size(4) == 2,
+              "als_sweep: V22 must be (", F, ", ", T, ", ", B,
+              ", 2, 2), got ", V22.sizes());
+  TORCH_CHECK(J.dim() == 6 && J.size(0) == F && J.size(2) == K
+              && J.size(4) == 2 && J.size(5) == 2,
+              "als_sweep: J must be (", F, ", Ts, ", K, ", N, 2, 2), got ",
+              J.sizes());
+  const int64_t Ts = J.size(1), N = J.size(3);
+  check_index(p_idx, at::kInt, B, "p_idx");
+  check_index(q_idx, at::kInt, B, "q_idx");
+  check_index(t_int, at::kInt, T, "t_int");
   // entry-major layout (F, X, 2TB): kernel writes coalesce across the
   // sample axis and the gather+sum reduces along the last dim
   auto rhs_cat = at::empty({F, 2L * 2 * K, 2L * T * B}, C22.options());
   auto nm_cat = at::empty({F, 4L * K * K, 2L * T * B}, C22.options());
   const long total = (long)F * T * B;
+  if (total == 0 || K == 0) return {rhs_cat, nm_cat};  // nothing to write
+  TORCH_CHECK(Ts >= 1 && N >= 1, "als_sweep: J holds no solutions");
+  TORCH_CHECK(T * B <= INT_MAX / 2 && F <= INT_MAX && Ts <= INT_MAX && N <= INT_MAX
+              && (total + 255) / 256 <= INT_MAX,
+              "als_sweep: too many samples");
   hipLaunchKernelGGL(als_sweep_kernel,
                      dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
                      stream(),
@@ -529,7 +566,8 @@ std::tuple<at::Tensor, at::Tensor> als_sweep(
                      t_int.data_ptr<int>(),
                      reinterpret_cast<c32b*>(rhs_cat.data_ptr()),
                      reinterpret_cast<c32b*>(nm_cat.data_ptr()),
-                     F, K, T, B, N, Ts);
+                     (int)F, (int)K, (int)T, (int)B, (int)N, (int)Ts);
+  check_launch("als_sweep_kernel");
   return {rhs_cat, nm_cat};
 }
 
@@ -882,41 +920,63 @@ void per_update(at::Tensor& priorities, const at::Tensor& idx,
 // elements: C[g] = A[g / rep] @ B[g]. The dsolutions hot op.
 at::Tensor cgemm_nn_bcast(const at::Tensor& A, const at::Tensor& B,
                           int64_t rep) {
-  TORCH_CHECK(A.is_cuda() && A.scalar_type() == at::kComplexFloat
-              && A.is_contiguous(), "A must be contiguous cfloat GPU");
-  TORCH_CHECK(B.is_cuda() && B.scalar_type() == at::kComplexFloat
-              && B.is_contiguous(), "B must be contiguous cfloat GPU");
-  const int KA = A.size(0), M = A.size(1), Kd = A.size(2);
-  const int G = B.size(0), N = B.size(2);
+  check_c64(A, "A");
+  check_c64(B, "B");
+  TORCH_CHECK(A.dim() == 3 && B.dim() == 3,
+              "cgemm: A must be (KA, M, K) and B (G, K, N), got ", A.sizes(),
+              " and ", B.sizes());
+  TORCH_CHECK(rep >= 1, "cgemm: rep must be at least 1, got ", rep);
+  const int64_t KA = A.size(0), M = A.size(1), Kd = A.size(2);
+  const int64_t G = B.size(0), N = B.size(2);
   TORCH_CHECK(B.size(1) == Kd, "cgemm K mismatch");
   TORCH_CHECK(G == KA * rep, "cgemm batch/rep mismatch");
-  auto C = at::empty({G, M, N}, A.options());
-  dim3 grid((M + 63) / 64, (N + 15) / 16, G);
+  TORCH_CHECK(M <= INT_MAX - 64 && Kd <= INT_MAX - 32 && N <= INT_MAX - 16,
+              "cgemm: matrix too large");
+  // an empty sum is zero
+  auto C = Kd == 0 ? at::zeros({G, M, N}, A.options())
+                   : at::empty({G, M, N}, A.options());
+  if (G == 0 || M == 0 || N == 0 || Kd == 0) return C;
+  TORCH_CHECK((N + 15) / 16 <= 65535 && G <= 65535,
+              "cgemm grid limits: N = ", N, ", G = ", G);
+  dim3 grid((unsigned)((M + 63) / 64), (unsigned)((N + 15) / 16),
+            (unsigned)G);
   hipLaunchKernelGGL(cgemm_nn_bcast_kernel, grid, dim3(256), 0, stream(),
                      reinterpret_cast<const float*>(A.data_ptr()),
                      reinterpret_cast<const float*>(B.data_ptr()),
                      reinterpret_cast<float*>(C.data_ptr()),
-                     M, Kd, N, G, (int)rep);
+                     (int)M, (int)Kd, (int)N, (int)G, (int)rep);
+  check_launch("cgemm_nn_bcast_kernel");
   return C;
 }
 
 // Fused gather + segment-sum (the ALS per-station reduction).
 at::Tensor gather_sum(const at::Tensor& in, const at::Tensor& gidx) {
-  TORCH_CHECK(in.is_cuda() && in.scalar_type() == at::kComplexFloat
-              && in.is_contiguous(), "in must be contiguous cfloat");
-  TORCH_CHECK(gidx.scalar_type() == at::kLong && gidx.is_contiguous(),
-              "gidx must be contiguous int64");
-  const int F = in.size(0), X = in.size(1);
+  check_c64(in, "in");
+  TORCH_CHECK(gidx.is_cuda() && gidx.scalar_type() == at::kLong
+              && gidx.is_contiguous(),
+              "gidx must be contiguous int64 on the GPU");
+  TORCH_CHECK(in.dim() == 3 && gidx.dim() == 2,
+              "gather_sum: in must be (F, X, S) and gidx (G, Cnt), got ",
+              in.sizes(), " and ", gidx.sizes());
+  const int64_t F = in.size(0), X = in.size(1);
   const long S = in.size(2);
-  const int G = gidx.size(0), Cnt = gidx.size(1);
-  auto out = at::empty({F, X, G}, in.options());
+  const int64_t G = gidx.size(0), Cnt = gidx.size(1);
   const long total = (long)F * X * G;
+  // an empty sum is zero
+  auto out = Cnt == 0 ? at::zeros({F, X, G}, in.options())
+                      : at::empty({F, X, G}, in.options());
+  if (total == 0 || Cnt == 0) return out;
+  TORCH_CHECK(S >= 1, "gather_sum: indices into an empty axis");
+  TORCH_CHECK(F <= INT_MAX && X <= INT_MAX && G <= INT_MAX
+              && Cnt <= INT_MAX && (total + 3) / 4 <= INT_MAX,
+              "gather_sum: too many outputs");
   hipLaunchKernelGGL(gather_sum_kernel,
                      dim3((unsigned)((total + 3) / 4)), dim3(256), 0,
                      stream(), reinterpret_cast<const c32b*>(in.data_ptr()),
                      gidx.data_ptr<long>(),
-                     reinterpret_cast<c32b*>(out.data_ptr()), F, X, S, G,
-                     Cnt);
+                     reinterpret_cast<c32b*>(out.data_ptr()), (int)F, (int)X,
+                     S, (int)G, (int)Cnt);
+  check_launch("gather_sum_kernel");
   return out;
 }
 
@@ -928,16 +988,22 @@ at::Tensor two_loop_apply(const at::Tensor& Y, const at::Tensor& S,
   check_f32(S, "S");
   check_f32(Q, "Q");
   check_f32(ro, "ro");
-  const int h = Y.size(0);
+  TORCH_CHECK(Y.dim() == 2 && S.dim() == 2 && Q.dim() == 2 && ro.dim() == 1,
+              "two_loop: Y, S must be (h, n), Q (m, n), ro (h,)");
+  const int64_t h = Y.size(0);
   const long n = Y.size(1);
-  const int m = Q.size(0);
+  const int64_t m = Q.size(0);
   TORCH_CHECK(h <= 16, "two_loop: history <= 16");
   TORCH_CHECK(Q.size(1) == n && S.sizes() == Y.sizes(), "shape mismatch");
+  TORCH_CHECK(ro.size(0) == h, "two_loop: ro must hold one entry per pair");
   auto R = at::empty_like(Q);
-  hipLaunchKernelGGL(two_loop_kernel, dim3(m), dim3(256), 0, stream(),
-                     Y.data_ptr<float>(), S.data_ptr<float>(),
+  if (m == 0 || n == 0) return R;  // no right-hand side: nothing to launch
+  TORCH_CHECK(m <= INT_MAX, "two_loop: too many right-hand sides");
+  hipLaunchKernelGGL(two_loop_kernel, dim3((unsigned)m), dim3(256), 0,
+                     stream(), Y.data_ptr<float>(), S.data_ptr<float>(),
                      Q.data_ptr<float>(), R.data_ptr<float>(),
-                     ro.data_ptr<float>(), (float)gamma, h, n, m);
+                     ro.data_ptr<float>(), (float)gamma, (int)h, n, (int)m);
+  check_launch("two_loop_kernel");
   return R;
 }
 
@@ -945,23 +1011,52 @@ at::Tensor two_loop_apply(const at::Tensor& Y, const at::Tensor& S,
 at::Tensor hessianres(const at::Tensor& C, const at::Tensor& R,
                       const at::Tensor& J, const at::Tensor& p_idx,
                       const at::Tensor& q_idx, int64_t N) {
-  TORCH_CHECK(C.is_cuda() && C.scalar_type() == at::kComplexFloat
-              && C.is_contiguous(), "C must be contiguous cfloat");
-  TORCH_CHECK(R.is_contiguous() && J.is_contiguous(), "contiguous");
-  TORCH_CHECK(p_idx.scalar_type() == at::kInt, "p_idx int32");
-  const int K = C.size(0);
-  const int S = C.size(1);
-  const int B = N * (N - 1) / 2;
-  const int T = S / B;
+  check_c64(C, "C");
+  check_c64(R, "R");
+  check_c64(J, "J");
+  TORCH_CHECK(N >= 2 && N <= 32768, "hessianres: N must be in [2, 32768], "
+              "got ", N);
+  TORCH_CHECK(C.dim() == 3 && C.size(2) == 4,
+              "hessianres: C must be (K, T*B, 4), got ", C.sizes());
+  const int64_t K = C.size(0);
+  const int64_t S = C.size(1);
+  const int64_t B = N * (N - 1) / 2;
+  TORCH_CHECK(S >= 1 && S % B == 0, "hessianres: ", S,
+              " samples are no positive multiple of the ", B, " baselines");
+  TORCH_CHECK(S <= INT_MAX / 4, "hessianres: too many samples");
+  const int64_t T = S / B;
+  TORCH_CHECK((R.dim() == 2 && R.size(0) == 2 * S && R.size(1) == 2)
+              || (R.dim() == 3 && R.size(0) == S && R.size(1) == 2
+                  && R.size(2) == 2),
+              "hessianres: R must be (2*T*B, 2) or (T*B, 2, 2), got ",
+              R.sizes());
+  TORCH_CHECK((J.dim() == 3 && J.size(0) == K && J.size(1) == 2 * N
+               && J.size(2) == 2)
+              || (J.dim() == 4 && J.size(0) == K && J.size(1) == N
+                  && J.size(2) == 2 && J.size(3) == 2),
+              "hessianres: J must be (K, 2N, 2) or (K, N, 2, 2), got ",
+              J.sizes());
+  check_index(p_idx, at::kInt, B, "p_idx");
+  check_index(q_idx, at::kInt, B, "q_idx");
+  TORCH_CHECK(K <= 65535, "hessianres grid limit: K = ", K);
   auto H = at::zeros({K, 4 * N, 4 * N}, C.options());
-  dim3 grid((B + 3) / 4, K);
+  if (K == 0) return H;
+  dim3 grid((unsigned)((B + 3) / 4), (unsigned)K);
   hipLaunchKernelGGL(hessianres_kernel, grid, dim3(64), 0, stream(),
                      reinterpret_cast<const c32h2*>(C.data_ptr()),
                      reinterpret_cast<const c32h2*>(R.data_ptr()),
                      reinterpret_cast<const c32h2*>(J.data_ptr()),
                      p_idx.data_ptr<int>(), q_idx.data_ptr<int>(),
                      reinterpret_cast<c32h2*>(H.data_ptr()),
-                     K, (int)N, B, T);
+                     (int)K, (int)N, (int)B, (int)T);
+  check_launch("hessianres_kernel");
+  // the diagonal blocks hold unscaled sums: scale them once
+  const long diag = (long)K * N * 16;
+  hipLaunchKernelGGL(hessianres_scale_diag_kernel,
+                     dim3((unsigned)((diag + 255) / 256)), dim3(256), 0,
+                     stream(), reinterpret_cast<c32h2*>(H.data_ptr()),
+                     (int)K, (int)N, (int)B, (int)T);
+  check_launch("hessianres_scale_diag_kernel");
   return H;
 }
 

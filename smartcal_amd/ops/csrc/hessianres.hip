@@ -15,7 +15,10 @@
 // with Ci the column-major 2x2 view of C[k, t*B+b, :] and G_p/G_q
 // t-independent (J is per solution interval). All scaled by 1/(B·T).
 // Off/mirror blocks are unique per (p,q) -> direct stores; diagonal
-// blocks accumulate across baselines -> float atomics.
+// blocks accumulate across baselines -> float atomics of the unscaled
+// sums, scaled once by hessianres_scale_diag_kernel afterwards: an entry
+// then carries the roundings of its sum and two for the scale, not two
+// per baseline.
 
 #include "common.h"
 
@@ -124,11 +127,29 @@ extern "C" __global__ __launch_bounds__(64) void hessianres_kernel(
   if (a == c) {
     float* dst1 = reinterpret_cast<float*>(
         &Hk[(4L * p + row) * ld + 4L * p + col]);
-    atomicAdd(dst1 + 0, d1.x * inv);
-    atomicAdd(dst1 + 1, d1.y * inv);
+    atomicAdd(dst1 + 0, d1.x);
+    atomicAdd(dst1 + 1, d1.y);
     float* dst2 = reinterpret_cast<float*>(
         &Hk[(4L * q + row) * ld + 4L * q + col]);
-    atomicAdd(dst2 + 0, d2.x * inv);
-    atomicAdd(dst2 + 1, d2.y * inv);
+    atomicAdd(dst2 + 0, d2.x);
+    atomicAdd(dst2 + 1, d2.y);
   }
+}
+
+// Scale the K·N diagonal 4x4 blocks of H by 1/(B·T), one thread per
+// element, after hessianres_kernel on the same stream.
+extern "C" __global__ __launch_bounds__(256) void
+hessianres_scale_diag_kernel(c32h* __restrict__ H, int K, int N, int B,
+                             int T) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (long)K * N * 16) return;
+  const int e = (int)(idx & 15);
+  const long kn = idx >> 4;
+  const int n = (int)(kn % N);
+  const long k = kn / N;
+  const float inv = 1.f / ((float)B * (float)T);
+  const long ld = 4L * N;
+  c32h* h = H + k * ld * ld + (4L * n + (e >> 2)) * ld + 4L * n + (e & 3);
+  h->x *= inv;
+  h->y *= inv;
 }

@@ -74,6 +74,60 @@ def _poly_basis(freqs: np.ndarray, f_all: np.ndarray, f0: float, Ne: int,
     return B
 
 
+def _als_contributions_torch(data22, C22, J, p_idx, q_idx, t_int):
+    """Per-sample normal-equation contributions of one ALS sweep, the
+    torch composition of ops/csrc/als_sweep.hip: (rhs_cat (F, 2·2K, 2TB),
+    nm_cat (F, 2K·2K, 2TB)), the p-side samples in columns [0, TB), the
+    q-side ones in [TB, 2TB)."""
+    F, T, Bn = data22.shape[0], data22.shape[1], data22.shape[2]
+    K = C22.shape[1]
+    # A^k for p-side rows: A = C_pq (J^k_q)^H ; for q-side rows:
+    # A' = C_pq^H (J^k_p)^H  (from V_pq^H = Σ J^k_q C^H J_p^H)
+    Jt = J[:, t_int]                               # (F,T,K,N,2,2)
+    Jq = Jt[:, :, :, q_idx]                        # (F,T,K,B,2,2)
+    Jp = Jt[:, :, :, p_idx]
+    Cp = C22.permute(0, 2, 3, 1, 4, 5)             # (F,T,B,K,2,2)
+    # elementwise small-complex products (radio.small_complex):
+    # batched 2×2 / k=2 shapes are pathological for rocBLAS
+    from .small_complex import mm2H, Hmm2, abH_k2
+    A_p = mm2H(Cp, Jq.permute(0, 1, 3, 2, 4, 5))   # (F,T,B,K,2,2)
+    A_q = Hmm2(Cp, Jp.permute(0, 1, 3, 2, 4, 5).conj().mT)
+    V = data22                                      # (F,T,B,2,2)
+    # per (station, interval): normal matrix (2K,2K), rhs (2,2K)
+    # W = A stacked over k → (2K,2); contribs V·W^H and W·W^H
+    Wp = A_p.reshape(F, T, Bn, 2 * K, 2)
+    Wq = A_q.reshape(F, T, Bn, 2 * K, 2)
+    rhs_p = abH_k2(V, Wp)                           # (F,T,B,2,2K)
+    rhs_q = abH_k2(V.mH, Wq)
+    nm_p = abH_k2(Wp, Wp)                           # (F,T,B,2K,2K)
+    nm_q = abH_k2(Wq, Wq)
+    rhs_cat = torch.cat(
+        [rhs_p.reshape(F, T * Bn, 2 * 2 * K),
+         rhs_q.reshape(F, T * Bn, 2 * 2 * K)], dim=1) \
+        .permute(0, 2, 1)
+    nm_cat = torch.cat(
+        [nm_p.reshape(F, T * Bn, 2 * K * 2 * K),
+         nm_q.reshape(F, T * Bn, 2 * K * 2 * K)], dim=1) \
+        .permute(0, 2, 1)
+    return rhs_cat, nm_cat
+
+
+def _gather_plan(t_int, p_idx, q_idx, N, Ts):
+    """Gather plan (Ts·N, Cnt) for the per-(interval, station) reduction:
+    station n of interval ti receives exactly Cnt = Tdelta·(N−1)
+    contributions (as the p side or the q side of a baseline).
+    Precomputing the gather indices into cat([p-side, q-side]) turns four
+    slow complex index_add_ scatters per sweep into two coalesced
+    gather+sum passes."""
+    T, Bn = t_int.shape[0], p_idx.shape[0]
+    flat_p = (t_int.view(T, 1) * N + p_idx.view(1, Bn)).reshape(-1)
+    flat_q = (t_int.view(T, 1) * N + q_idx.view(1, Bn)).reshape(-1)
+    both = torch.cat([flat_p, flat_q])              # (2·T·B,)
+    order = torch.argsort(both, stable=True)
+    Cnt = T * Bn * 2 // (Ts * N)                    # = Tdelta·(N−1)
+    return order.reshape(Ts * N, Cnt)               # (Ts·N, Cnt)
+
+
 def _solve_sweeps(data22, C22, J, rho_t, prox_target, p_idx, q_idx, N,
                   Tdelta, n_sweeps, lambda_reg=1e-6):
     """In-place alternating-LS sweeps for J (F?,Ts,K,N,2,2).
@@ -85,20 +139,18 @@ def _solve_sweeps(data22, C22, J, rho_t, prox_target, p_idx, q_idx, N,
     F, T, Bn = data22.shape[0], data22.shape[1], data22.shape[2]
     K = C22.shape[1]
     Ts = J.shape[1]
+    if T != Ts * Tdelta:
+        # the gather plan below gives every (interval, station) the same
+        # number of contributions; a longer last interval would be cut at
+        # the wrong places and solved wrongly without any sign of it
+        raise ValueError(
+            f"_solve_sweeps: {T} timeslots are not {Ts} solution intervals "
+            f"of {Tdelta}")
     dev = data22.device
     t_int = (torch.arange(T, device=dev) // Tdelta).clamp_(max=Ts - 1)
     eyeK = torch.eye(2 * K, dtype=data22.dtype, device=dev)
-    # gather plan for the per-(interval, station) reduction: station n of
-    # interval ti receives exactly Tdelta·(N−1) contributions (as the p
-    # side or the q side of a baseline). Precomputing the gather indices
-    # into cat([p-side, q-side]) turns four slow complex index_add_
-    # scatters per sweep into two coalesced gather+sum passes.
-    flat_p = (t_int.view(T, 1) * N + p_idx.view(1, Bn)).reshape(-1)
-    flat_q = (t_int.view(T, 1) * N + q_idx.view(1, Bn)).reshape(-1)
-    both = torch.cat([flat_p, flat_q])              # (2·T·B,)
-    order = torch.argsort(both, stable=True)
-    Cnt = T * Bn * 2 // (Ts * N)                    # = Tdelta·(N−1)
-    gidx = order.reshape(Ts * N, Cnt)               # (Ts·N, Cnt)
+    gidx = _gather_plan(t_int, p_idx, q_idx, N, Ts)
+    Cnt = gidx.shape[1]
     use_kernel = dev.type == "cuda" and K <= 8
     if use_kernel:
         from ..ops import ext
@@ -115,34 +167,8 @@ def _solve_sweeps(data22, C22, J, rho_t, prox_target, p_idx, q_idx, N,
             rhs_cat, nm_cat = ext().als_sweep(
                 C22c, data22.contiguous(), J.contiguous(), p32, q32, t32)
         else:
-            # A^k for p-side rows: A = C_pq (J^k_q)^H ; for q-side rows:
-            # A' = C_pq^H (J^k_p)^H  (from V_pq^H = Σ J^k_q C^H J_p^H)
-            Jt = J[:, t_int]                               # (F,T,K,N,2,2)
-            Jq = Jt[:, :, :, q_idx]                        # (F,T,K,B,2,2)
-            Jp = Jt[:, :, :, p_idx]
-            Cp = C22.permute(0, 2, 3, 1, 4, 5)             # (F,T,B,K,2,2)
-            # elementwise small-complex products (radio.small_complex):
-            # batched 2×2 / k=2 shapes are pathological for rocBLAS
-            from .small_complex import mm2H, Hmm2, abH_k2
-            A_p = mm2H(Cp, Jq.permute(0, 1, 3, 2, 4, 5))   # (F,T,B,K,2,2)
-            A_q = Hmm2(Cp, Jp.permute(0, 1, 3, 2, 4, 5).conj().mT)
-            V = data22                                      # (F,T,B,2,2)
-            # per (station, interval): normal matrix (2K,2K), rhs (2,2K)
-            # W = A stacked over k → (2K,2); contribs V·W^H and W·W^H
-            Wp = A_p.reshape(F, T, Bn, 2 * K, 2)
-            Wq = A_q.reshape(F, T, Bn, 2 * K, 2)
-            rhs_p = abH_k2(V, Wp)                           # (F,T,B,2,2K)
-            rhs_q = abH_k2(V.mH, Wq)
-            nm_p = abH_k2(Wp, Wp)                           # (F,T,B,2K,2K)
-            nm_q = abH_k2(Wq, Wq)
-            rhs_cat = torch.cat(
-                [rhs_p.reshape(F, T * Bn, 2 * 2 * K),
-                 rhs_q.reshape(F, T * Bn, 2 * 2 * K)], dim=1) \
-                .permute(0, 2, 1)
-            nm_cat = torch.cat(
-                [nm_p.reshape(F, T * Bn, 2 * K * 2 * K),
-                 nm_q.reshape(F, T * Bn, 2 * K * 2 * K)], dim=1) \
-                .permute(0, 2, 1)
+            rhs_cat, nm_cat = _als_contributions_torch(
+                data22, C22, J, p_idx, q_idx, t_int)
         # reduce into (F,Ts,N,…) by interval and station via the
         # precomputed gather plan (see above); cat layout is (F, X, 2TB)
         if use_kernel:
