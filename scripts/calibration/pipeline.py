@@ -47,6 +47,19 @@ def main():
     ap.add_argument("--imager", default="grid", choices=["grid", "dft"],
                     help="grid: nearest-cell gridder + FFT; dft: exact "
                          "direct Fourier sum with the w-term")
+    ap.add_argument("--robust", action="store_true",
+                    help="robust (Student's-t) noise model in calibration")
+    ap.add_argument("--nulow", default=2.0, type=float,
+                    help="lower bound of the robust nu (sagecal -L)")
+    ap.add_argument("--nuhigh", default=30.0, type=float,
+                    help="upper bound of the robust nu (sagecal -H)")
+    ap.add_argument("--uvmin", default=None, type=float,
+                    help="lower uv cut in wavelengths (sagecal -x)")
+    ap.add_argument("--uvmax", default=None, type=float,
+                    help="upper uv cut in wavelengths (sagecal -y)")
+    ap.add_argument("--rfi", default=0.0, type=float,
+                    help="fraction of samples given unflagged outliers of "
+                         "50 x the data RMS")
     args = ap.parse_args()
     rng = np.random.default_rng(args.seed)
     device = "cuda" if torch.cuda.is_available() else "cpu"
@@ -70,6 +83,14 @@ def main():
                                    device=device, rng=rng,
                                    torch_seed=args.seed,
                                    beam_elements=elements)
+    if args.rfi > 0:
+        # a generator of its own, as for --beam
+        gen = torch.Generator(device=device)
+        gen.manual_seed(int(np.random.default_rng(
+            [args.seed, 0x0F1]).integers(2 ** 31)))
+        vis, rfi_mask = sim.add_outliers(vis, args.rfi, 50.0, gen)
+        print(f"[rfi] {int(rfi_mask.sum())} of {rfi_mask.numel()} samples "
+              f"corrupted")
     print(f"[simulate] {args.stations} stations, {args.nf} sub-bands, "
           f"{vis.S} samples/band: {time.time() - t0:.2f} s")
     if args.save_vis:
@@ -77,8 +98,21 @@ def main():
 
     t0 = time.time()
     rho = np.full(args.K, args.rho, np.float32)
+    wopts = {}
+    if args.robust:
+        wopts.update(robust=True, nulow=args.nulow, nuhigh=args.nuhigh)
+    if args.uvmin is not None:
+        wopts["uvmin"] = args.uvmin
+    if args.uvmax is not None:
+        wopts["uvmax"] = args.uvmax
     sol = solver.calibrate(vis, sky_cal, cs_cal, rho, admm_iter=args.admm,
-                           poly_order=args.poly)
+                           poly_order=args.poly, **wopts)
+    if sol.weights is not None:
+        msg = f"[weights] mean {float(sol.weights.mean()):.3f}, " \
+              f"{int((sol.weights == 0).sum())} samples at 0"
+        if sol.nu is not None:
+            msg += f", nu {[round(float(x), 2) for x in sol.nu]}"
+        print(msg)
     res_pow = float(torch.linalg.vector_norm(sol.residual))
     dat_pow = float(torch.linalg.vector_norm(vis.data))
     print(f"[calibrate] -A {args.admm} -P {args.poly}: residual/data "

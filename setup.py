@@ -37,6 +37,7 @@ sources = [str(CSRC / f) for f in [
     "hessianres.hip",
     "two_loop.hip",
     "gather_sum.hip",
+    "robust.hip",
 ]]
 
 setup(

@@ -55,8 +55,21 @@ class CalibEnv(gymapi.Env):
                  diffuse_beta: float | None = None,
                  station_beam: bool = False, beam_elements: int = 48,
                  imager: str = "grid", image_fov: float | None = None,
-                 image_wterm: bool = True):
+                 image_wterm: bool = True, robust: bool = False,
+                 uvmin: float | None = None, rfi_fraction: float = 0.0,
+                 rfi_amplitude: float = 50.0):
         super().__init__()
+        # robust (Student's-t) noise model and lower uv cut in wavelengths
+        # of the calibration (`radio.solver.calibrate`; the reference's
+        # `docal.sh` passes `-L 2 -x 30`), and unflagged interference in
+        # the simulated data (`radio.sim.add_outliers`), drawn from a
+        # generator of its own like the beam's element layouts
+        self.robust = robust
+        self.uvmin = uvmin
+        self.rfi_fraction = rfi_fraction
+        self.rfi_amplitude = rfi_amplitude
+        self.rfi_rng = np.random.default_rng(
+            None if seed is None else [seed, 0x0F1])
         if imager not in ("grid", "dft"):
             raise ValueError(f"imager must be 'grid' or 'dft', got "
                              f"{imager!r}")
@@ -120,6 +133,11 @@ class CalibEnv(gymapi.Env):
             snr=self.snr, device=self.device, rng=self.rng,
             torch_seed=int(self.rng.integers(2 ** 31)),
             beam_elements=elements)
+        if self.rfi_fraction > 0:
+            gen = torch.Generator(device=self.device)
+            gen.manual_seed(int(self.rfi_rng.integers(2 ** 31)))
+            vis, _ = rsim.add_outliers(vis, self.rfi_fraction,
+                                       self.rfi_amplitude, gen)
         # cache calibration-model coherencies per freq (constant per episode)
         C = torch.stack([
             predict_coherencies_uvw(sky_cal, cs_cal, vis.uvw, float(f),
@@ -129,6 +147,16 @@ class CalibEnv(gymapi.Env):
                               C=C, skylmn=skylmn, rho0=rho0,
                               f_low=freqs[0] / 1e6, f_high=freqs[-1] / 1e6)
 
+    def _weight_options(self) -> dict:
+        """Keywords of `calibrate` for the robust model and the uv cut;
+        empty by default, so that the default call is today's."""
+        kw = {}
+        if self.robust:
+            kw["robust"] = True
+        if self.uvmin is not None:
+            kw["uvmin"] = self.uvmin
+        return kw
+
     def _calibrate_and_observe(self):
         sc = self._scenario
         vis: rsim.VisData = sc["vis"]
@@ -137,14 +165,20 @@ class CalibEnv(gymapi.Env):
             vis, sc["sky"], sc["clusters"], self.rho_spectral[:K],
             admm_iter=self.admm_iter, poly_order=self.poly_order,
             alpha=float(np.mean(self.rho_spatial[:K])),
-            C_cache=sc["C"])
+            C_cache=sc["C"], **self._weight_options())
         # data / residual dirty images (σ over the mean image, à la
         # calmean + fits std in `calibenv.py:148-158`)
         inf_idx = np.linspace(0, self.Nf - 1, self.inf_nfreq).astype(int)
         f0 = float(np.mean(vis.freqs))
-        sI_d = [0.5 * (vis.data[fi][:, 0] + vis.data[fi][:, 3])
-                for fi in range(self.Nf)]
-        sI_r = [0.5 * (sol.residual[fi][:, 0] + sol.residual[fi][:, 3])
+        # flagged samples are left out of every image
+        def unflagged(sI, fi):
+            if vis.flags is None:
+                return sI
+            return sI * (~vis.flags[fi]).to(torch.float32)
+        sI_d = [unflagged(0.5 * (vis.data[fi][:, 0] + vis.data[fi][:, 3]),
+                          fi) for fi in range(self.Nf)]
+        sI_r = [unflagged(0.5 * (sol.residual[fi][:, 0]
+                                 + sol.residual[fi][:, 3]), fi)
                 for fi in range(self.Nf)]
         sI_i = []
         for fi in inf_idx:
@@ -154,7 +188,7 @@ class CalibEnv(gymapi.Env):
             vals = rinf.influence_values(sol.residual[fi], sc["C"][fi],
                                          sol.J_ref_layout(int(fi)), vis.N,
                                          vis.Tdelta, Hadd)
-            sI_i.append(0.5 * (vals[:, 0] + vals[:, 3]))
+            sI_i.append(unflagged(0.5 * (vals[:, 0] + vals[:, 3]), int(fi)))
         if self.imager == "dft":
             # two launches: data + residual maps of all bands (M = 2),
             # then the influence maps of the inf_nfreq bands

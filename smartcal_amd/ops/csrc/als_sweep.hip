@@ -14,27 +14,22 @@
 
 #define KMAX 8
 
-typedef struct {
-  float x, y;
-} c32;
-
-__device__ __forceinline__ c32 cmul(c32 a, c32 b) {
-  return {a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x};
-}
-__device__ __forceinline__ c32 cmulj(c32 a, c32 b) {  // a * conj(b)
-  return {a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y};
-}
-__device__ __forceinline__ c32 cjmul(c32 a, c32 b) {  // conj(a) * b
-  return {a.x * b.x + a.y * b.y, a.x * b.y - a.y * b.x};
-}
-__device__ __forceinline__ c32 cadd(c32 a, c32 b) {
-  return {a.x + b.x, a.y + b.y};
+// One body, two instances: als_sweep_kernel minimises the plain sum of
+// squares; als_sweep_w_kernel the weighted one, sum_s w_s |V_s - model|^2,
+// where every entry a sample contributes is its unweighted value times
+// w_s (one more coalesced load and a multiply before each store).
+template <bool WEIGHTED>
+__device__ __forceinline__ c32 als_out(c32 v, float ws) {
+  if (WEIGHTED) return {v.x * ws, v.y * ws};
+  return v;
 }
 
-extern "C" __global__ void als_sweep_kernel(
+template <bool WEIGHTED>
+__device__ __forceinline__ void als_sweep_body(
     const c32* __restrict__ C22,   // (F,K,T,B,2,2)
     const c32* __restrict__ V22,   // (F,T,B,2,2)
     const c32* __restrict__ J,     // (F,Ts,K,N,2,2)
+    const float* __restrict__ w,   // (F,T,B) sample weights, if WEIGHTED
     const int* __restrict__ p_idx, // (B,)
     const int* __restrict__ q_idx, // (B,)
     const int* __restrict__ t_int, // (T,)
@@ -44,6 +39,7 @@ extern "C" __global__ void als_sweep_kernel(
   const long s = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long TB = (long)T * B;
   if (s >= (long)F * TB) return;
+  const float ws = WEIGHTED ? w[s] : 1.f;
   const int f = (int)(s / TB);
   const long tb = s % TB;
   const int t = (int)(tb / B);
@@ -109,12 +105,12 @@ extern "C" __global__ void als_sweep_kernel(
       for (int i = 0; i < 2; ++i) {
         c32 vp = cadd(cmulj(V[i][0], Ap[k][j][0]),
                       cmulj(V[i][1], Ap[k][j][1]));
-        rp[(long)(i * K2 + 2 * k + j) * TB2] = vp;
+        rp[(long)(i * K2 + 2 * k + j) * TB2] = als_out<WEIGHTED>(vp, ws);
         // rhs_q uses V^H: (V^H)[i][t] = conj(V[t][i])
         // rhs_q[i][c] = sum_t conj(V[t][i]) * conj(Aq[c][t])
         c32 vq = cadd(cmulj((c32){V[0][i].x, -V[0][i].y}, Aq[k][j][0]),
                       cmulj((c32){V[1][i].x, -V[1][i].y}, Aq[k][j][1]));
-        rq[(long)(i * K2 + 2 * k + j) * TB2] = vq;
+        rq[(long)(i * K2 + 2 * k + j) * TB2] = als_out<WEIGHTED>(vq, ws);
       }
     }
   }
@@ -133,14 +129,34 @@ extern "C" __global__ void als_sweep_kernel(
 #pragma unroll
         for (int jc = 0; jc < 2; ++jc) {
           const int c = 2 * kc + jc;
-          np_[(long)(r * K2 + c) * TB2] =
+          np_[(long)(r * K2 + c) * TB2] = als_out<WEIGHTED>(
               cadd(cmulj(Ap[kr][jr][0], Ap[kc][jc][0]),
-                   cmulj(Ap[kr][jr][1], Ap[kc][jc][1]));
-          nq_[(long)(r * K2 + c) * TB2] =
+                   cmulj(Ap[kr][jr][1], Ap[kc][jc][1])), ws);
+          nq_[(long)(r * K2 + c) * TB2] = als_out<WEIGHTED>(
               cadd(cmulj(Aq[kr][jr][0], Aq[kc][jc][0]),
-                   cmulj(Aq[kr][jr][1], Aq[kc][jc][1]));
+                   cmulj(Aq[kr][jr][1], Aq[kc][jc][1])), ws);
         }
       }
     }
   }
+}
+
+extern "C" __global__ void als_sweep_kernel(
+    const c32* __restrict__ C22, const c32* __restrict__ V22,
+    const c32* __restrict__ J, const int* __restrict__ p_idx,
+    const int* __restrict__ q_idx, const int* __restrict__ t_int,
+    c32* __restrict__ rhs_cat, c32* __restrict__ nm_cat,
+    int F, int K, int T, int B, int N, int Ts) {
+  als_sweep_body<false>(C22, V22, J, nullptr, p_idx, q_idx, t_int, rhs_cat,
+                        nm_cat, F, K, T, B, N, Ts);
+}
+
+extern "C" __global__ void als_sweep_w_kernel(
+    const c32* __restrict__ C22, const c32* __restrict__ V22,
+    const c32* __restrict__ J, const float* __restrict__ w,
+    const int* __restrict__ p_idx, const int* __restrict__ q_idx,
+    const int* __restrict__ t_int, c32* __restrict__ rhs_cat,
+    c32* __restrict__ nm_cat, int F, int K, int T, int B, int N, int Ts) {
+  als_sweep_body<true>(C22, V22, J, w, p_idx, q_idx, t_int, rhs_cat, nm_cat,
+                       F, K, T, B, N, Ts);
 }

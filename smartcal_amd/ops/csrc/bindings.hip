@@ -55,6 +55,13 @@ struct c32b { float x, y; };
 extern "C" __global__ void als_sweep_kernel(
     const c32b*, const c32b*, const c32b*, const int*, const int*,
     const int*, c32b*, c32b*, int, int, int, int, int, int);
+extern "C" __global__ void als_sweep_w_kernel(
+    const c32b*, const c32b*, const c32b*, const float*, const int*,
+    const int*, const int*, c32b*, c32b*, int, int, int, int, int, int);
+extern "C" __global__ void vis_residual_weights_kernel(
+    const c32b*, const c32b*, const c32b*, const float*, const float*,
+    const float*, const int*, const int*, const int*, c32b*, float*, float*,
+    double*, int, int, int, int, int);
 extern "C" __global__ void enet_influence_kernel(
     const float*, const float*, const float*, const float*, const float*,
     const int*, const float*, const float*, float*, float*, int, int, int);
@@ -520,29 +527,36 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> conv2d_k5s2_bwd(
 }
 
 // Fused ALS-sweep contributions for the calibration solver: one launch
-// instead of ~100 elementwise kernels per sweep (radio/solver.py).
-std::tuple<at::Tensor, at::Tensor> als_sweep(
-    const at::Tensor& C22, const at::Tensor& V22, const at::Tensor& J,
-    const at::Tensor& p_idx, const at::Tensor& q_idx,
-    const at::Tensor& t_int) {
+// instead of ~100 elementwise kernels per sweep (radio/solver.py). With
+// weights w (F, T, B) every entry of a sample is scaled by its weight
+// (als_sweep_w_kernel, the weighted instance of the same body).
+std::tuple<at::Tensor, at::Tensor> als_sweep_impl(
+    const char* who, const at::Tensor& C22, const at::Tensor& V22,
+    const at::Tensor& J, const at::Tensor* w, const at::Tensor& p_idx,
+    const at::Tensor& q_idx, const at::Tensor& t_int) {
   check_c64(C22, "C22");
   check_c64(V22, "V22");
   check_c64(J, "J");
   TORCH_CHECK(C22.dim() == 6 && C22.size(4) == 2 && C22.size(5) == 2,
-              "als_sweep: C22 must be (F, K, T, B, 2, 2), got ",
-              C22.sizes());
+              who, ": C22 must be (F, K, T, B, 2, 2), got ", C22.sizes());
   const int64_t F = C22.size(0), K = C22.size(1), T = C22.size(2),
                 B = C22.size(3);
-  TORCH_CHECK(K <= 8, "als_sweep supports K <= 8");
+  TORCH_CHECK(K <= 8, who, " supports K <= 8");
   TORCH_CHECK(V22.dim() == 5 && V22.size(0) == F && V22.size(1) == T
               && V22.size(2) == B && V22.size(3) == 2 && V22.size(4) == 2,
-              "als_sweep: V22 must be (", F, ", ", T, ", ", B,
+              who, ": V22 must be (", F, ", ", T, ", ", B,
               ", 2, 2), got ", V22.sizes());
   TORCH_CHECK(J.dim() == 6 && J.size(0) == F && J.size(2) == K
               && J.size(4) == 2 && J.size(5) == 2,
-              "als_sweep: J must be (", F, ", Ts, ", K, ", N, 2, 2), got ",
+              who, ": J must be (", F, ", Ts, ", K, ", N, 2, 2), got ",
               J.sizes());
   const int64_t Ts = J.size(1), N = J.size(3);
+  if (w) {
+    check_f32(*w, "w");
+    TORCH_CHECK(w->dim() == 3 && w->size(0) == F && w->size(1) == T
+                && w->size(2) == B, who, ": w must be (", F, ", ", T, ", ",
+                B, "), got ", w->sizes());
+  }
   check_index(p_idx, at::kInt, B, "p_idx");
   check_index(q_idx, at::kInt, B, "q_idx");
   check_index(t_int, at::kInt, T, "t_int");
@@ -552,23 +566,114 @@ std::tuple<at::Tensor, at::Tensor> als_sweep(
   auto nm_cat = at::empty({F, 4L * K * K, 2L * T * B}, C22.options());
   const long total = (long)F * T * B;
   if (total == 0 || K == 0) return {rhs_cat, nm_cat};  // nothing to write
-  TORCH_CHECK(Ts >= 1 && N >= 1, "als_sweep: J holds no solutions");
+  TORCH_CHECK(Ts >= 1 && N >= 1, who, ": J holds no solutions");
   TORCH_CHECK(T * B <= INT_MAX / 2 && F <= INT_MAX && Ts <= INT_MAX && N <= INT_MAX
               && (total + 255) / 256 <= INT_MAX,
-              "als_sweep: too many samples");
-  hipLaunchKernelGGL(als_sweep_kernel,
-                     dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
+              who, ": too many samples");
+  const dim3 grid((unsigned)((total + 255) / 256));
+  const auto* Cp = reinterpret_cast<const c32b*>(C22.data_ptr());
+  const auto* Vp = reinterpret_cast<const c32b*>(V22.data_ptr());
+  const auto* Jp = reinterpret_cast<const c32b*>(J.data_ptr());
+  auto* rhs_p = reinterpret_cast<c32b*>(rhs_cat.data_ptr());
+  auto* nm_p = reinterpret_cast<c32b*>(nm_cat.data_ptr());
+  if (w) {
+    hipLaunchKernelGGL(als_sweep_w_kernel, grid, dim3(256), 0, stream(),
+                       Cp, Vp, Jp, w->data_ptr<float>(),
+                       p_idx.data_ptr<int>(), q_idx.data_ptr<int>(),
+                       t_int.data_ptr<int>(), rhs_p, nm_p,
+                       (int)F, (int)K, (int)T, (int)B, (int)N, (int)Ts);
+    check_launch("als_sweep_w_kernel");
+  } else {
+    hipLaunchKernelGGL(als_sweep_kernel, grid, dim3(256), 0, stream(),
+                       Cp, Vp, Jp, p_idx.data_ptr<int>(),
+                       q_idx.data_ptr<int>(), t_int.data_ptr<int>(), rhs_p,
+                       nm_p, (int)F, (int)K, (int)T, (int)B, (int)N, (int)Ts);
+    check_launch("als_sweep_kernel");
+  }
+  return {rhs_cat, nm_cat};
+}
+
+std::tuple<at::Tensor, at::Tensor> als_sweep(
+    const at::Tensor& C22, const at::Tensor& V22, const at::Tensor& J,
+    const at::Tensor& p_idx, const at::Tensor& q_idx,
+    const at::Tensor& t_int) {
+  return als_sweep_impl("als_sweep", C22, V22, J, nullptr, p_idx, q_idx,
+                        t_int);
+}
+
+std::tuple<at::Tensor, at::Tensor> als_sweep_w(
+    const at::Tensor& C22, const at::Tensor& V22, const at::Tensor& J,
+    const at::Tensor& w, const at::Tensor& p_idx, const at::Tensor& q_idx,
+    const at::Tensor& t_int) {
+  return als_sweep_impl("als_sweep_w", C22, V22, J, &w, p_idx, q_idx, t_int);
+}
+
+// Residual r = V - sum_k J_p C_k J_q^H, its squared norm e2, the robust
+// weight w = m (nu + 8) / (nu + e2 / sigma2) and the float64 per-block
+// partial sums (F, nblk, 4) of m, w e2, w and m (ln w - w), in one launch
+// (robust.hip). nu and sigma2 are per-frequency device arrays.
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor>
+vis_residual_weights(const at::Tensor& C22, const at::Tensor& V22,
+                     const at::Tensor& J, const at::Tensor& m,
+                     const at::Tensor& nu, const at::Tensor& sigma2,
+                     const at::Tensor& p_idx, const at::Tensor& q_idx,
+                     const at::Tensor& t_int) {
+  const char* who = "vis_residual_weights";
+  check_c64(C22, "C22");
+  check_c64(V22, "V22");
+  check_c64(J, "J");
+  check_f32(m, "m");
+  check_f32(nu, "nu");
+  check_f32(sigma2, "sigma2");
+  TORCH_CHECK(C22.dim() == 6 && C22.size(4) == 2 && C22.size(5) == 2,
+              who, ": C22 must be (F, K, T, B, 2, 2), got ", C22.sizes());
+  const int64_t F = C22.size(0), K = C22.size(1), T = C22.size(2),
+                B = C22.size(3);
+  TORCH_CHECK(V22.dim() == 5 && V22.size(0) == F && V22.size(1) == T
+              && V22.size(2) == B && V22.size(3) == 2 && V22.size(4) == 2,
+              who, ": V22 must be (", F, ", ", T, ", ", B,
+              ", 2, 2), got ", V22.sizes());
+  TORCH_CHECK(J.dim() == 6 && J.size(0) == F && J.size(2) == K
+              && J.size(4) == 2 && J.size(5) == 2,
+              who, ": J must be (", F, ", Ts, ", K, ", N, 2, 2), got ",
+              J.sizes());
+  const int64_t Ts = J.size(1), N = J.size(3);
+  TORCH_CHECK(m.dim() == 3 && m.size(0) == F && m.size(1) == T
+              && m.size(2) == B, who, ": m must be (", F, ", ", T, ", ", B,
+              "), got ", m.sizes());
+  TORCH_CHECK(nu.dim() == 1 && nu.size(0) == F, who, ": nu must be (", F,
+              ",), got ", nu.sizes());
+  TORCH_CHECK(sigma2.dim() == 1 && sigma2.size(0) == F, who,
+              ": sigma2 must be (", F, ",), got ", sigma2.sizes());
+  check_index(p_idx, at::kInt, B, "p_idx");
+  check_index(q_idx, at::kInt, B, "q_idx");
+  check_index(t_int, at::kInt, T, "t_int");
+  const int64_t TB = T * B, nblk = (TB + 255) / 256;
+  auto r = at::empty({F, TB, 4}, C22.options());
+  auto e2 = at::empty({F, T, B}, m.options());
+  auto w = at::empty({F, T, B}, m.options());
+  // every block writes its four sums, so nothing is zeroed beforehand
+  auto part = at::empty({F, nblk, 4}, m.options().dtype(at::kDouble));
+  if (F == 0 || TB == 0) return {r, e2, w, part};      // nothing to write
+  TORCH_CHECK(K == 0 || (Ts >= 1 && N >= 1), who, ": J holds no solutions");
+  TORCH_CHECK(F <= 65535, who, " grid limit: F = ", F);
+  TORCH_CHECK(TB <= INT_MAX / 2 && K <= INT_MAX && Ts <= INT_MAX
+              && N <= INT_MAX, who, ": too many samples");
+  hipLaunchKernelGGL(vis_residual_weights_kernel,
+                     dim3((unsigned)nblk, (unsigned)F), dim3(256), 0,
                      stream(),
                      reinterpret_cast<const c32b*>(C22.data_ptr()),
                      reinterpret_cast<const c32b*>(V22.data_ptr()),
                      reinterpret_cast<const c32b*>(J.data_ptr()),
-                     p_idx.data_ptr<int>(), q_idx.data_ptr<int>(),
-                     t_int.data_ptr<int>(),
-                     reinterpret_cast<c32b*>(rhs_cat.data_ptr()),
-                     reinterpret_cast<c32b*>(nm_cat.data_ptr()),
-                     (int)F, (int)K, (int)T, (int)B, (int)N, (int)Ts);
-  check_launch("als_sweep_kernel");
-  return {rhs_cat, nm_cat};
+                     m.data_ptr<float>(), nu.data_ptr<float>(),
+                     sigma2.data_ptr<float>(), p_idx.data_ptr<int>(),
+                     q_idx.data_ptr<int>(), t_int.data_ptr<int>(),
+                     reinterpret_cast<c32b*>(r.data_ptr()),
+                     e2.data_ptr<float>(), w.data_ptr<float>(),
+                     part.data_ptr<double>(), (int)K, (int)T, (int)B, (int)N,
+                     (int)Ts);
+  check_launch("vis_residual_weights_kernel");
+  return {r, e2, w, part};
 }
 
 // Direct-accumulate variant of fused_linear_bwd_dz: dgamma/dbeta are
@@ -1405,6 +1510,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("Ws"), py::arg("bs"), py::arg("gammas"), py::arg("betas"),
         py::arg("acts"), py::arg("save") = true);
   m.def("als_sweep", &als_sweep);
+  m.def("als_sweep_w", &als_sweep_w);
+  m.def("vis_residual_weights", &vis_residual_weights);
   m.def("conv2d_k5s2_fwd", &conv2d_k5s2_fwd);
   m.def("conv2d_k5s2_bwd", &conv2d_k5s2_bwd);
   m.def("tanh_gauss_fwd", &tanh_gauss_fwd);

@@ -52,6 +52,25 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// complex64 as a float pair and its products, for the 2x2 Jones algebra
+// of als_sweep.hip and robust.hip
+typedef struct {
+  float x, y;
+} c32;
+
+__device__ __forceinline__ c32 cmul(c32 a, c32 b) {
+  return {a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x};
+}
+__device__ __forceinline__ c32 cmulj(c32 a, c32 b) {  // a * conj(b)
+  return {a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y};
+}
+__device__ __forceinline__ c32 cjmul(c32 a, c32 b) {  // conj(a) * b
+  return {a.x * b.x + a.y * b.y, a.x * b.y - a.y * b.x};
+}
+__device__ __forceinline__ c32 cadd(c32 a, c32 b) {
+  return {a.x + b.x, a.y + b.y};
+}
+
 // fp32 MFMA accumulator fragment: v_mfma_f32_16x16x4_f32.
 // Lane l supplies A[i = l&15][k = l>>4] and B[k = l>>4][j = l&15];
 // C/D: col = l&15, row = (l>>4)*4 + reg, reg in [0,4).

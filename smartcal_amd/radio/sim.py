@@ -27,7 +27,8 @@ from .hessian import baseline_pq
 from .shapelet import generate_random_shapelet_model, load_shapelet_model
 
 __all__ = ["ATEAM", "VisData", "make_calibration_sky", "make_demixing_sky",
-           "simulate_observation", "apply_jones", "add_noise", "to_R"]
+           "simulate_observation", "apply_jones", "add_noise",
+           "add_outliers", "to_R"]
 
 # The five A-team outlier sources (name, ra rad, dec rad, flux Jy at 150MHz)
 # — positions as in the reference's base sky model
@@ -63,6 +64,7 @@ class VisData:
     model: torch.Tensor | None = None     # (Nf, S, 4) noiseless, optional
     J_true: np.ndarray | None = None      # (Nf, K, 2N·Ts, 2) ground truth
     beam: arr.StationBeam | None = None   # station beam the data went through
+    flags: torch.Tensor | None = None     # (Nf, S) bool, True = left out
 
     @property
     def B(self) -> int:
@@ -273,6 +275,26 @@ def add_noise(V: torch.Tensor, snr: float,
     noise = torch.view_as_complex(nr)
     scale = torch.linalg.vector_norm(V) / (snr * torch.linalg.vector_norm(noise))
     return V + noise * scale, float(scale)
+
+
+def add_outliers(vis: VisData, fraction: float, amplitude: float,
+                 gen: torch.Generator | None = None
+                 ) -> tuple[VisData, torch.Tensor]:
+    """Unflagged interference: complex Gaussian outliers of
+    ``amplitude`` × RMS(data) per component added to a random ``fraction``
+    of the (frequency, sample) pairs, all four correlations of a pair
+    together. Returns (a new VisData sharing everything but ``data``, the
+    (Nf, S) bool mask of the corrupted pairs); flags are not set."""
+    from dataclasses import replace
+    data = vis.data
+    Nf, S = data.shape[0], data.shape[1]
+    dev = data.device
+    mask = torch.rand((Nf, S), generator=gen, device=dev) < fraction
+    rms = torch.sqrt(torch.mean(data.abs().square()))
+    z = torch.view_as_complex(
+        torch.randn(data.shape + (2,), generator=gen, device=dev))
+    out = data + (amplitude * rms) * z * mask.unsqueeze(-1)
+    return replace(vis, data=out), mask
 
 
 def simulate_observation(layout: arr.StationLayout, sky: SkyModel,
