@@ -23,6 +23,7 @@ sources = [str(CSRC / f) for f in [
     "fused_linear.hip",
     "gemm_f32.hip",
     "elementwise.hip",
+    "sac_glue.hip",
     "enet_solver.hip",
     "als_sweep.hip",
     "conv2d.hip",

@@ -40,6 +40,39 @@ extern "C" __global__ void fused_adam_kernel(float*, const float*, float*,
                                              float*, float*, float, float,
                                              float, float, long);
 extern "C" __global__ void adam_bump_kernel(float*);
+extern "C" __global__ void tanh_gauss_head_fwd_kernel(const float*,
+                                                      const float*, float*,
+                                                      float*, float*, float,
+                                                      float, float, int, int);
+extern "C" __global__ void tanh_gauss_head_bwd_kernel(
+    const float*, const float*, const float*, const float*, const float*,
+    float*, float, float, float, int, int);
+extern "C" __global__ void fused_adam_polyak2_kernel(AdamPolyak2Args, float,
+                                                     float, float, float,
+                                                     float, long);
+extern "C" __global__ void adam_bump2_kernel(float*, float*);
+extern "C" __global__ void sac_critic_loss_fwd_kernel(
+    const float*, const float*, const float*, const float*, const float*,
+    const float*, const bool*, const float*, float, float*, float*, int);
+extern "C" __global__ void sac_critic_loss_bwd_kernel(const float*,
+                                                      const float*,
+                                                      const float*,
+                                                      const float*, float,
+                                                      float*, float*, int);
+extern "C" __global__ void sac_actor_loss_fwd_kernel(const float*,
+                                                     const float*,
+                                                     const float*,
+                                                     const float*, float*,
+                                                     int);
+extern "C" __global__ void sac_actor_loss_bwd_kernel(const float*,
+                                                     const float*,
+                                                     const float*,
+                                                     const float*, float,
+                                                     float*, float*, float*,
+                                                     int);
+extern "C" __global__ void replay_gather_kernel(
+    const long*, const float*, const float*, const float*, const float*,
+    const bool*, float, float*, float*, float*, float*, bool*, int, int);
 extern "C" __global__ void enet_lbfgs_solve_kernel(
     const float*, const float*, const float*, float*, float*, float*, int*,
     int, int, int, int, int, int);
@@ -922,6 +955,275 @@ void fused_adam(at::Tensor& p, const at::Tensor& g, at::Tensor& m,
   check_launch("adam_bump_kernel");
 }
 
+// The sampler on the actor head's raw output (B, 2A): slice, clamp and
+// sample in one launch. Returns (action, logprob, tanh(z)).
+std::tuple<at::Tensor, at::Tensor, at::Tensor> tanh_gauss_head_fwd(
+    const at::Tensor& out, const at::Tensor& eps, double max_action,
+    double lo, double hi) {
+  check_f32(out, "out");
+  check_f32(eps, "eps");
+  TORCH_CHECK(out.dim() == 2 && out.size(1) % 2 == 0,
+              "tanh_gauss_head_fwd: out must be (B, 2A)");
+  const int B = out.size(0), A = out.size(1) / 2;
+  TORCH_CHECK(eps.dim() == 2 && eps.size(0) == B && eps.size(1) == A,
+              "tanh_gauss_head_fwd: eps must be (B, A)");
+  auto action = at::empty_like(eps);
+  auto at_ = at::empty_like(eps);
+  // a row without actions sums to log-probability 0
+  auto logp = A == 0 ? at::zeros({B, 1}, out.options())
+                     : at::empty({B, 1}, out.options());
+  if (B == 0 || A == 0) return {action, logp, at_};
+  hipLaunchKernelGGL(tanh_gauss_head_fwd_kernel, dim3(B), dim3(64), 0,
+                     stream(), out.data_ptr<float>(), eps.data_ptr<float>(),
+                     action.data_ptr<float>(), logp.data_ptr<float>(),
+                     at_.data_ptr<float>(), (float)max_action, (float)lo,
+                     (float)hi, B, A);
+  check_launch("tanh_gauss_head_fwd_kernel");
+  return {action, logp, at_};
+}
+
+at::Tensor tanh_gauss_head_bwd(const at::Tensor& dact,
+                               const at::Tensor& dlogp,
+                               const at::Tensor& out, const at::Tensor& eps,
+                               const at::Tensor& at_, double max_action,
+                               double lo, double hi) {
+  check_f32(dact, "dact");
+  check_f32(dlogp, "dlogp");
+  check_f32(out, "out");
+  check_f32(eps, "eps");
+  check_f32(at_, "at");
+  TORCH_CHECK(dact.dim() == 2, "tanh_gauss_head_bwd: dact must be (B, A)");
+  TORCH_CHECK(eps.sizes() == dact.sizes() && at_.sizes() == dact.sizes(),
+              "tanh_gauss_head_bwd: eps and at must have dact's shape");
+  const int B = dact.size(0), A = dact.size(1);
+  TORCH_CHECK(out.dim() == 2 && out.size(0) == B && out.size(1) == 2 * A,
+              "tanh_gauss_head_bwd: out must be (B, 2A)");
+  TORCH_CHECK(dlogp.numel() == B,
+              "tanh_gauss_head_bwd: dlogp must hold B values");
+  auto dout = at::empty_like(out);
+  const long n = (long)B * A;
+  if (n == 0) return dout;
+  hipLaunchKernelGGL(tanh_gauss_head_bwd_kernel, dim3((n + 255) / 256),
+                     dim3(256), 0, stream(), dact.data_ptr<float>(),
+                     dlogp.data_ptr<float>(), out.data_ptr<float>(),
+                     eps.data_ptr<float>(), at_.data_ptr<float>(),
+                     dout.data_ptr<float>(), (float)max_action, (float)lo,
+                     (float)hi, B, A);
+  check_launch("tanh_gauss_head_bwd_kernel");
+  return dout;
+}
+
+// Adam on two equal-sized pools and the polyak update of their targets in
+// one launch, then one bump of both step counters.
+void fused_adam_polyak2(at::Tensor& p0, const at::Tensor& g0, at::Tensor& m0,
+                        at::Tensor& v0, at::Tensor& t0, at::Tensor& tgt0,
+                        at::Tensor& p1, const at::Tensor& g1, at::Tensor& m1,
+                        at::Tensor& v1, at::Tensor& t1, at::Tensor& tgt1,
+                        double lr, double b1, double b2, double eps,
+                        double tau) {
+  const at::Tensor* all[] = {&p0, &g0, &m0, &v0, &tgt0,
+                             &p1, &g1, &m1, &v1, &tgt1};
+  const long n = p0.numel();
+  for (const at::Tensor* t : all) {
+    check_f32(*t, "fused_adam_polyak2 pool");
+    TORCH_CHECK(t->numel() == n,
+                "fused_adam_polyak2: every pool must hold as many values as "
+                "p0");
+  }
+  check_f32(t0, "t0");
+  check_f32(t1, "t1");
+  TORCH_CHECK(t0.numel() == 1 && t1.numel() == 1,
+              "fused_adam_polyak2: t0 and t1 are one step counter each");
+  if (n == 0) return;  // no parameters, no step: the counters stay too
+  AdamPolyak2Args a;
+  a.P0 = p0.data_ptr<float>();
+  a.P1 = p1.data_ptr<float>();
+  a.G0 = g0.data_ptr<float>();
+  a.G1 = g1.data_ptr<float>();
+  a.M0 = m0.data_ptr<float>();
+  a.M1 = m1.data_ptr<float>();
+  a.V0 = v0.data_ptr<float>();
+  a.V1 = v1.data_ptr<float>();
+  a.t0 = t0.data_ptr<float>();
+  a.t1 = t1.data_ptr<float>();
+  a.T0 = tgt0.data_ptr<float>();
+  a.T1 = tgt1.data_ptr<float>();
+  hipLaunchKernelGGL(fused_adam_polyak2_kernel, dim3((n + 255) / 256, 2),
+                     dim3(256), 0, stream(), a, (float)lr, (float)b1,
+                     (float)b2, (float)eps, (float)tau, n);
+  check_launch("fused_adam_polyak2_kernel");
+  hipLaunchKernelGGL(adam_bump2_kernel, dim3(1), dim3(64), 0, stream(),
+                     t0.data_ptr<float>(), t1.data_ptr<float>());
+  check_launch("adam_bump2_kernel");
+}
+
+// A (B, 1) fp32 column of the SAC losses.
+inline void check_col(const at::Tensor& t, int64_t B, const char* name) {
+  check_f32(t, name);
+  TORCH_CHECK(t.dim() == 2 && t.size(0) == B && t.size(1) == 1, name,
+              " must be (", B, ", 1), got ", t.sizes());
+}
+
+// A 0-dim or one-element fp32 device scalar (alpha, the loss's gradient).
+inline void check_scalar(const at::Tensor& t, const char* name) {
+  check_f32(t, name);
+  TORCH_CHECK(t.numel() == 1, name, " must hold one value");
+}
+
+// Returns (loss, new_q_value).
+std::tuple<at::Tensor, at::Tensor> sac_critic_loss_fwd(
+    const at::Tensor& q1, const at::Tensor& q2, const at::Tensor& q1_t,
+    const at::Tensor& q2_t, const at::Tensor& logp, const at::Tensor& reward,
+    const at::Tensor& done, const at::Tensor& alpha, double gamma) {
+  TORCH_CHECK(q1.dim() == 2 && q1.size(0) > 0,
+              "sac_critic_loss_fwd: q1 must be (B, 1) with B > 0");
+  const int64_t B = q1.size(0);
+  check_col(q1, B, "q1");
+  check_col(q2, B, "q2");
+  check_col(q1_t, B, "q1_t");
+  check_col(q2_t, B, "q2_t");
+  check_col(logp, B, "logp");
+  check_col(reward, B, "reward");
+  TORCH_CHECK(done.is_cuda() && done.scalar_type() == at::kBool
+              && done.is_contiguous() && done.numel() == B,
+              "done must hold B contiguous bools on the GPU");
+  check_scalar(alpha, "alpha");
+  auto y = at::empty_like(q1);
+  auto loss = at::empty({}, q1.options());
+  hipLaunchKernelGGL(sac_critic_loss_fwd_kernel, dim3(1), dim3(256), 0,
+                     stream(), q1.data_ptr<float>(), q2.data_ptr<float>(),
+                     q1_t.data_ptr<float>(), q2_t.data_ptr<float>(),
+                     logp.data_ptr<float>(), reward.data_ptr<float>(),
+                     done.data_ptr<bool>(), alpha.data_ptr<float>(),
+                     (float)gamma, y.data_ptr<float>(),
+                     loss.data_ptr<float>(), (int)B);
+  check_launch("sac_critic_loss_fwd_kernel");
+  return {loss, y};
+}
+
+// Returns (dq1, dq2).
+std::tuple<at::Tensor, at::Tensor> sac_critic_loss_bwd(
+    const at::Tensor& q1, const at::Tensor& q2, const at::Tensor& y,
+    const at::Tensor& grad) {
+  TORCH_CHECK(q1.dim() == 2 && q1.size(0) > 0,
+              "sac_critic_loss_bwd: q1 must be (B, 1) with B > 0");
+  const int64_t B = q1.size(0);
+  check_col(q1, B, "q1");
+  check_col(q2, B, "q2");
+  check_col(y, B, "new_q_value");
+  check_scalar(grad, "grad");
+  auto dq1 = at::empty_like(q1);
+  auto dq2 = at::empty_like(q2);
+  // mse_loss's backward scales by 2/B, formed in double and cast
+  hipLaunchKernelGGL(sac_critic_loss_bwd_kernel, dim3((B + 255) / 256),
+                     dim3(256), 0, stream(), q1.data_ptr<float>(),
+                     q2.data_ptr<float>(), y.data_ptr<float>(),
+                     grad.data_ptr<float>(), (float)(2.0 / (double)B),
+                     dq1.data_ptr<float>(), dq2.data_ptr<float>(), (int)B);
+  check_launch("sac_critic_loss_bwd_kernel");
+  return {dq1, dq2};
+}
+
+at::Tensor sac_actor_loss_fwd(const at::Tensor& q1, const at::Tensor& q2,
+                              const at::Tensor& logp,
+                              const at::Tensor& alpha) {
+  TORCH_CHECK(q1.dim() == 2 && q1.size(0) > 0,
+              "sac_actor_loss_fwd: q1 must be (B, 1) with B > 0");
+  const int64_t B = q1.size(0);
+  check_col(q1, B, "q1");
+  check_col(q2, B, "q2");
+  check_col(logp, B, "logp");
+  check_scalar(alpha, "alpha");
+  auto loss = at::empty({}, q1.options());
+  hipLaunchKernelGGL(sac_actor_loss_fwd_kernel, dim3(1), dim3(256), 0,
+                     stream(), q1.data_ptr<float>(), q2.data_ptr<float>(),
+                     logp.data_ptr<float>(), alpha.data_ptr<float>(),
+                     loss.data_ptr<float>(), (int)B);
+  check_launch("sac_actor_loss_fwd_kernel");
+  return loss;
+}
+
+// Returns (dq1, dq2, dlogp).
+std::tuple<at::Tensor, at::Tensor, at::Tensor> sac_actor_loss_bwd(
+    const at::Tensor& q1, const at::Tensor& q2, const at::Tensor& alpha,
+    const at::Tensor& grad) {
+  TORCH_CHECK(q1.dim() == 2 && q1.size(0) > 0,
+              "sac_actor_loss_bwd: q1 must be (B, 1) with B > 0");
+  const int64_t B = q1.size(0);
+  check_col(q1, B, "q1");
+  check_col(q2, B, "q2");
+  check_scalar(alpha, "alpha");
+  check_scalar(grad, "grad");
+  auto dq1 = at::empty_like(q1);
+  auto dq2 = at::empty_like(q1);
+  auto dlogp = at::empty_like(q1);
+  // mean's backward divides by B as a product with the float reciprocal
+  hipLaunchKernelGGL(sac_actor_loss_bwd_kernel, dim3((B + 255) / 256),
+                     dim3(256), 0, stream(), q1.data_ptr<float>(),
+                     q2.data_ptr<float>(), alpha.data_ptr<float>(),
+                     grad.data_ptr<float>(), 1.0f / (float)B,
+                     dq1.data_ptr<float>(), dq2.data_ptr<float>(),
+                     dlogp.data_ptr<float>(), (int)B);
+  check_launch("sac_actor_loss_bwd_kernel");
+  return {dq1, dq2, dlogp};
+}
+
+// One replay batch in one launch. idx is not range-checked on the device:
+// the caller draws it with randint(0, n), n <= rows, which guarantees it.
+void replay_gather(const at::Tensor& idx, const at::Tensor& state_mem,
+                   const at::Tensor& new_state_mem,
+                   const at::Tensor& action_mem,
+                   const at::Tensor& reward_mem,
+                   const at::Tensor& terminal_mem, double scale,
+                   at::Tensor& out_state, at::Tensor& out_new_state,
+                   at::Tensor& out_action, at::Tensor& out_reward,
+                   at::Tensor& out_done) {
+  check_f32(state_mem, "state_mem");
+  check_f32(new_state_mem, "new_state_mem");
+  check_f32(action_mem, "action_mem");
+  check_f32(reward_mem, "reward_mem");
+  check_f32(out_state, "out_state");
+  check_f32(out_new_state, "out_new_state");
+  check_f32(out_action, "out_action");
+  check_f32(out_reward, "out_reward");
+  TORCH_CHECK(out_state.dim() >= 1, "replay_gather: out_state must be (B, D)");
+  const int64_t B = out_state.size(0);
+  check_index(idx, at::kLong, B, "idx");
+  TORCH_CHECK(state_mem.dim() >= 1 && state_mem.size(0) > 0,
+              "replay_gather: state_mem must have rows");
+  const int64_t rows = state_mem.size(0);
+  const int64_t D = state_mem.numel() / rows;
+  const int64_t A = action_mem.numel() / rows;
+  TORCH_CHECK(new_state_mem.numel() == rows * D
+              && action_mem.numel() == rows * A
+              && reward_mem.numel() == rows && terminal_mem.numel() == rows,
+              "replay_gather: the memories must have the same number of rows");
+  TORCH_CHECK(terminal_mem.is_cuda() && terminal_mem.scalar_type() == at::kBool
+              && terminal_mem.is_contiguous(),
+              "terminal_mem must be contiguous bools on the GPU");
+  TORCH_CHECK(out_done.is_cuda() && out_done.scalar_type() == at::kBool
+              && out_done.is_contiguous() && out_done.numel() == B,
+              "out_done must hold B contiguous bools on the GPU");
+  TORCH_CHECK(out_state.numel() == B * D && out_new_state.numel() == B * D
+              && out_action.numel() == B * A && out_reward.numel() == B,
+              "replay_gather: the outputs must be B rows of the memories' "
+              "widths");
+  if (B == 0) return;
+  hipLaunchKernelGGL(replay_gather_kernel, dim3(B), dim3(256), 0, stream(),
+                     (const long*)idx.data_ptr<int64_t>(),
+                     state_mem.data_ptr<float>(),
+                     new_state_mem.data_ptr<float>(),
+                     action_mem.data_ptr<float>(),
+                     reward_mem.data_ptr<float>(),
+                     terminal_mem.data_ptr<bool>(), (float)scale,
+                     out_state.data_ptr<float>(),
+                     out_new_state.data_ptr<float>(),
+                     out_action.data_ptr<float>(),
+                     out_reward.data_ptr<float>(),
+                     out_done.data_ptr<bool>(), (int)D, (int)A);
+  check_launch("replay_gather_kernel");
+}
+
 std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> enet_lbfgs_solve(
     const at::Tensor& A, const at::Tensor& y, const at::Tensor& rho,
     int64_t epochs, int64_t max_iter, int64_t history) {
@@ -1517,6 +1819,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("tanh_gauss_fwd", &tanh_gauss_fwd);
   m.def("tanh_gauss_bwd", &tanh_gauss_bwd);
   m.def("fused_adam", &fused_adam);
+  m.def("tanh_gauss_head_fwd", &tanh_gauss_head_fwd);
+  m.def("tanh_gauss_head_bwd", &tanh_gauss_head_bwd);
+  m.def("fused_adam_polyak2", &fused_adam_polyak2);
+  m.def("sac_critic_loss_fwd", &sac_critic_loss_fwd);
+  m.def("sac_critic_loss_bwd", &sac_critic_loss_bwd);
+  m.def("sac_actor_loss_fwd", &sac_actor_loss_fwd);
+  m.def("sac_actor_loss_bwd", &sac_actor_loss_bwd);
+  m.def("replay_gather", &replay_gather);
   m.def("enet_lbfgs_solve", &enet_lbfgs_solve);
   m.def("enet_influence", &enet_influence);
   m.def("per_sample", &per_sample);

@@ -112,6 +112,17 @@ struct ChainArgs {
 // widest LDS activation row: 512 columns + one 64-wide tile of zero pad
 #define CHAIN_XMAX 576
 
+// The two pools of fused_adam_polyak2_kernel (elementwise.hip): parameters,
+// gradients, Adam moments, device step counter and polyak target of each.
+struct AdamPolyak2Args {
+  float *P0, *P1;
+  const float *G0, *G1;
+  float *M0, *M1;
+  float *V0, *V1;
+  const float *t0, *t1;
+  float *T0, *T1;
+};
+
 // Activation codes shared with python (smartcal_amd/ops/linear.py).
 #define ACT_NONE 0
 #define ACT_ELU 1

@@ -39,6 +39,52 @@ class _TanhGaussFn(torch.autograd.Function):
         return dmu, dlogsigma, None, None
 
 
+class _TanhGaussHeadFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, out, eps, max_action: float, lo: float, hi: float):
+        action, logprob, a_t = ext().tanh_gauss_head_fwd(out, eps,
+                                                         max_action, lo, hi)
+        ctx.save_for_backward(out, eps, a_t)
+        ctx.consts = (max_action, lo, hi)
+        return action, logprob
+
+    @staticmethod
+    def backward(ctx, daction, dlogprob):
+        out, eps, a_t = ctx.saved_tensors
+        dout = ext().tanh_gauss_head_bwd(
+            daction.contiguous(), dlogprob.contiguous(), out, eps, a_t,
+            *ctx.consts)
+        return dout, None, None, None, None
+
+
+def tanh_gauss_head_sample(out: torch.Tensor, lo: float, hi: float,
+                           max_action: float = 1.0,
+                           reparameterize: bool = True,
+                           eps: Optional[torch.Tensor] = None
+                           ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``tanh_gauss_sample`` on the actor head's raw output ``out`` (B, 2A),
+    HIP tensors only: ``mu = out[:, :A]`` and ``logsigma = clamp(out[:, A:],
+    lo, hi)`` are read inside the kernel, and backward writes the gradient of
+    ``out`` in one pass. Same values and the same noise draw as slicing,
+    clamping and calling ``tanh_gauss_sample``."""
+    if out.dim() == 1:
+        out = out.unsqueeze(0)
+    mu = out[..., :out.shape[-1] // 2]      # a view: shape and dtype only
+    if eps is None:
+        eps = torch.randn_like(mu)
+    else:
+        eps = eps.to(mu.dtype).reshape(mu.shape)
+    out_c = out.contiguous()
+    eps_c = eps.contiguous()
+    if reparameterize:
+        return _TanhGaussHeadFn.apply(out_c, eps_c, float(max_action),
+                                      float(lo), float(hi))
+    with torch.no_grad():
+        action, logprob, _ = ext().tanh_gauss_head_fwd(
+            out_c, eps_c, float(max_action), float(lo), float(hi))
+    return action, logprob
+
+
 def tanh_gauss_sample(mu: torch.Tensor, logsigma: torch.Tensor,
                       max_action: float = 1.0,
                       reparameterize: bool = True,

@@ -26,7 +26,7 @@ import torch.nn as nn
 from ..ops import use_hip
 from ..ops.linear import (FusedLinear, fused_linear, fused_chain,
                           fused_critic, get_compute_dtype)
-from ..ops.sampling import tanh_gauss_sample
+from ..ops.sampling import tanh_gauss_head_sample, tanh_gauss_sample
 
 LOGSIG_MIN = -20.0
 LOGSIG_MAX = 2.0
@@ -68,6 +68,12 @@ class SACActorMLP(nn.Module):
         return mu, logsigma
 
     def sample_normal(self, state: torch.Tensor, reparameterize: bool = True):
+        from . import sac  # the switch lives there; sac imports this module
+        if use_hip(state) and not sac.FORCE_TORCH_GLUE:
+            # slice, clamp and sampler in one kernel on the raw head output
+            return tanh_gauss_head_sample(_actor_out(self, state),
+                                          LOGSIG_MIN, LOGSIG_MAX,
+                                          self.max_action, reparameterize)
         mu, logsigma = self.forward(state)
         if mu.dim() == 1:
             mu = mu.unsqueeze(0)

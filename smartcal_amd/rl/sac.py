@@ -25,10 +25,71 @@ import torch
 import torch.nn.functional as F
 
 from ..envs.enet import obs_to_state
+from ..ops import ext, use_hip
 from ..utils.device import default_device
 from ..utils.flatten import FlatParams, FusedAdam
 from .buffers import PERBuffer, ReplayBuffer
 from .networks import CriticMLP, SACActorMLP
+
+# Tests only: True forces the torch composition of the learn step's glue
+# (losses, actor-head slicing and clamping, separate Adam and polyak launches,
+# index_select gathers) instead of the native kernels, so both can be compared
+# inside one build. Never set in production.
+FORCE_TORCH_GLUE = False
+
+
+class _CriticLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q1, q2, q1_t, q2_t, logp_next, reward, done, alpha,
+                gamma: float):
+        loss, new_q_value = ext().sac_critic_loss_fwd(
+            q1, q2, q1_t, q2_t, logp_next, reward, done, alpha, gamma)
+        ctx.save_for_backward(q1, q2, new_q_value)
+        ctx.mark_non_differentiable(new_q_value)
+        ctx.set_materialize_grads(False)
+        return loss, new_q_value
+
+    @staticmethod
+    def backward(ctx, g, _):
+        q1, q2, new_q_value = ctx.saved_tensors
+        dq1, dq2 = ext().sac_critic_loss_bwd(q1, q2, new_q_value,
+                                             g.contiguous())
+        return dq1, dq2, None, None, None, None, None, None, None
+
+
+def sac_critic_loss(q1, q2, q1_t, q2_t, logp_next, reward, done, alpha,
+                    gamma):
+    """Soft target and twin-critic regression loss in one HIP launch each
+    way: ``y = reward + gamma * (done ? 0 : min(q1_t, q2_t) - alpha *
+    logp_next)`` and ``loss = mse(q1, y) + mse(q2, y)``. ``alpha`` is the
+    0-dim device tensor (read at run time, so a captured graph sees updates).
+    Returns ``(loss, y)``; gradients flow to ``q1`` and ``q2`` only, with
+    the values ``F.mse_loss``'s backward gives."""
+    return _CriticLossFn.apply(
+        q1.contiguous(), q2.contiguous(), q1_t.contiguous(),
+        q2_t.contiguous(), logp_next.contiguous(), reward.contiguous(),
+        done.contiguous(), alpha, float(gamma))
+
+
+class _ActorLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q1_pi, q2_pi, logp, alpha):
+        ctx.save_for_backward(q1_pi, q2_pi, alpha)
+        return ext().sac_actor_loss_fwd(q1_pi, q2_pi, logp, alpha)
+
+    @staticmethod
+    def backward(ctx, g):
+        q1_pi, q2_pi, alpha = ctx.saved_tensors
+        dq1, dq2, dlogp = ext().sac_actor_loss_bwd(q1_pi, q2_pi, alpha,
+                                                   g.contiguous())
+        return dq1, dq2, dlogp, None
+
+
+def sac_actor_loss(q1_pi, q2_pi, logp, alpha):
+    """``mean(alpha * logp - minimum(q1_pi, q2_pi))`` in one HIP launch each
+    way, with ``torch.minimum``'s derivative (ties split in halves)."""
+    return _ActorLossFn.apply(q1_pi.contiguous(), q2_pi.contiguous(),
+                              logp.contiguous(), alpha)
 
 
 class Agent:
@@ -207,27 +268,44 @@ class Agent:
             lambda: self.critic_1(state_batch, action_batch),
             lambda: self.critic_2(state_batch, action_batch),
             _t1, _t2)
-        with torch.no_grad():
-            min_next_target = torch.min(q1_t, q2_t) \
-                - self.alpha * new_log_probs
-            # masked_fill (not boolean indexing): same semantics as the
-            # reference's t[mask]=0 but static-shaped => graph-safe
-            min_next_target = min_next_target.masked_fill(terminal_batch,
-                                                          0.0)
-            new_q_value = reward_batch + self.gamma * min_next_target
-        if is_w is not None:
-            critic_1_loss = (is_w * (q1 - new_q_value).pow(2)).mean()
-            critic_2_loss = (is_w * (q2 - new_q_value).pow(2)).mean()
+        # plain SAC on a HIP device: the glue below runs as native kernels
+        native = (is_w is None and not self.use_hint
+                  and not FORCE_TORCH_GLUE and use_hip(q1))
+        if native:
+            critic_loss, new_q_value = sac_critic_loss(
+                q1, q2, q1_t, q2_t, new_log_probs, reward_batch,
+                terminal_batch, self.alpha, self.gamma)
         else:
-            critic_1_loss = F.mse_loss(q1, new_q_value)
-            critic_2_loss = F.mse_loss(q2, new_q_value)
-        critic_loss = critic_1_loss + critic_2_loss
+            with torch.no_grad():
+                min_next_target = torch.min(q1_t, q2_t) \
+                    - self.alpha * new_log_probs
+                # masked_fill (not boolean indexing): same semantics as the
+                # reference's t[mask]=0 but static-shaped => graph-safe
+                min_next_target = min_next_target.masked_fill(
+                    terminal_batch, 0.0)
+                new_q_value = reward_batch + self.gamma * min_next_target
+            if is_w is not None:
+                critic_1_loss = (is_w * (q1 - new_q_value).pow(2)).mean()
+                critic_2_loss = (is_w * (q2 - new_q_value).pow(2)).mean()
+            else:
+                critic_1_loss = F.mse_loss(q1, new_q_value)
+                critic_2_loss = F.mse_loss(q2, new_q_value)
+            critic_loss = critic_1_loss + critic_2_loss
         self.critic_1_opt.zero_grad()
         self.critic_2_opt.zero_grad()
         critic_loss.backward()
         self._sync_side_streams()
         self._grad_sync([self.critic_1_fp, self.critic_2_fp])
-        self._fork(self.critic_1_opt.step, self.critic_2_opt.step)
+        if native:
+            # both Adam steps and both polyak updates in one launch; nothing
+            # writes the critic pools or touches the target pools between
+            # here and the end of the step, where the polyak update used to
+            # run
+            FusedAdam.step_pair_polyak(
+                self.critic_1_opt, self.critic_2_opt,
+                self.target_critic_1_fp, self.target_critic_2_fp, self.tau)
+        else:
+            self._fork(self.critic_1_opt.step, self.critic_2_opt.step)
 
         actions, log_probs = self.actor.sample_normal(state_batch,
                                                       reparameterize=True)
@@ -242,9 +320,11 @@ class Agent:
         q1_pi, q2_pi = self._pair(
             lambda: self.critic_1(state_batch, actions),
             lambda: self.critic_2(state_batch, actions))
-        critic_value = torch.min(q1_pi, q2_pi)
-
-        actor_loss = (self.alpha * log_probs - critic_value).mean()
+        if native:
+            actor_loss = sac_actor_loss(q1_pi, q2_pi, log_probs, self.alpha)
+        else:
+            critic_value = torch.min(q1_pi, q2_pi)
+            actor_loss = (self.alpha * log_probs - critic_value).mean()
         if self.use_hint:
             gfun = torch.max(
                 self.zero_tensor,
@@ -261,14 +341,15 @@ class Agent:
         self._sync_side_streams()
         self._grad_sync([self.actor_fp])
         self.actor_opt.step()
-        self.update_network_parameters()
+        if not native:
+            self.update_network_parameters()
         return q1, new_q_value
 
     # -- hipGraph capture of the learn step -------------------------------
     def enable_cuda_graph(self):
         """Capture the whole learn step (forwards, backwards, fused Adam,
         polyak) into ONE hipGraph. Per learn step afterwards: one randint,
-        four index_select gathers into static buffers, one graph replay —
+        one gather launch into static buffers, one graph replay —
         instead of ~100 python-dispatched launches. Only for the plain
         (non-PER, non-hint) path and after the replay has batch_size
         entries."""
@@ -289,18 +370,7 @@ class Agent:
         # populate statics with a real sample so warmup trains on data
         n = len(mem)
         if n > 0:
-            torch.randint(0, n, (B,), device=self.device, out=self._g_idx)
-            torch.index_select(mem.state_memory, 0, self._g_idx,
-                               out=self._g_state)
-            torch.index_select(mem.new_state_memory, 0, self._g_idx,
-                               out=self._g_new_state)
-            torch.index_select(mem.action_memory, 0, self._g_idx,
-                               out=self._g_action)
-            torch.index_select(mem.reward_memory, 0, self._g_idx,
-                               out=self._g_reward.view(-1))
-            self._g_reward.mul_(self.scale)
-            torch.index_select(mem.terminal_memory, 0, self._g_idx,
-                               out=self._g_done.view(-1))
+            self._sample_statics(n)
 
         # warmup on a side stream (allocator + autograd settle)
         torch.cuda.synchronize()
@@ -321,16 +391,20 @@ class Agent:
                              self._g_done, self._g_hint)
         self._graph = g
 
-    def disable_cuda_graph(self):
-        """Drop a captured graph and return to the eager learn path
-        (used e.g. when ranks must agree on graphed vs eager mode)."""
-        self._graph = None
-
-    def _learn_graphed(self):
+    def _sample_statics(self, n):
+        """Draw a uniform batch from the first ``n`` replay rows into the
+        graph's static buffers, rewards scaled (the body expects that)."""
         mem = self.replaymem
-        n = len(mem)
         torch.randint(0, n, (self.batch_size,), device=self.device,
                       out=self._g_idx)
+        if not FORCE_TORCH_GLUE:
+            # one launch; randint(0, n) keeps every index below the rows
+            ext().replay_gather(
+                self._g_idx, mem.state_memory, mem.new_state_memory,
+                mem.action_memory, mem.reward_memory, mem.terminal_memory,
+                float(self.scale), self._g_state, self._g_new_state,
+                self._g_action, self._g_reward, self._g_done)
+            return
         torch.index_select(mem.state_memory, 0, self._g_idx,
                            out=self._g_state)
         torch.index_select(mem.new_state_memory, 0, self._g_idx,
@@ -339,9 +413,17 @@ class Agent:
                            out=self._g_action)
         torch.index_select(mem.reward_memory, 0, self._g_idx,
                            out=self._g_reward.view(-1))
-        self._g_reward.mul_(self.scale)  # body expects scaled rewards
+        self._g_reward.mul_(self.scale)
         torch.index_select(mem.terminal_memory, 0, self._g_idx,
                            out=self._g_done.view(-1))
+
+    def disable_cuda_graph(self):
+        """Drop a captured graph and return to the eager learn path
+        (used e.g. when ranks must agree on graphed vs eager mode)."""
+        self._graph = None
+
+    def _learn_graphed(self):
+        self._sample_statics(len(self.replaymem))
         self._graph.replay()
         self.learn_counter += 1
 

@@ -112,6 +112,29 @@ class FusedAdam:
             self.fp.flat.addcdiv_(mhat, vhat.sqrt().add_(self.eps),
                                   value=-self.lr)
 
+    @staticmethod
+    @torch.no_grad()
+    def step_pair_polyak(opt_a: "FusedAdam", opt_b: "FusedAdam",
+                         target_a: FlatParams, target_b: FlatParams,
+                         tau: float):
+        """One Adam step of two equal-sized HIP pools with equal
+        hyperparameters, and ``target <- lerp(target, pool, tau)`` on each
+        pool's target, in ONE launch plus one bump of both step counters —
+        the same values as ``opt_a.step(); opt_b.step()`` followed by
+        ``target_x.polyak_from(opt_x.fp, tau)``."""
+        from ..ops import ext
+        hyper = (opt_a.lr, opt_a.beta1, opt_a.beta2, opt_a.eps)
+        assert hyper == (opt_b.lr, opt_b.beta1, opt_b.beta2, opt_b.eps) \
+            and not opt_a.weight_decay and not opt_b.weight_decay, \
+            "step_pair_polyak: the two optimizers must be configured alike"
+        opt_a.step_count += 1
+        opt_b.step_count += 1
+        ext().fused_adam_polyak2(
+            opt_a.fp.flat, opt_a.fp.flat_grad, opt_a.m, opt_a.v, opt_a.t_dev,
+            target_a.flat,
+            opt_b.fp.flat, opt_b.fp.flat_grad, opt_b.m, opt_b.v, opt_b.t_dev,
+            target_b.flat, *hyper, float(tau))
+
     def state_dict(self):
         return {"step": self.step_count, "m": self.m, "v": self.v,
                 "lr": self.lr, "t_dev": self.t_dev}
